@@ -14,6 +14,12 @@ accumulation (fp32 master weights rounded once per step); tanh jets, loss, reduc
 optimizer are fp32.  ``--precision bf16x3`` measures the split-activation kernels.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--npts 50000 | --global-npts G]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the throughput figure needs and nothing else: set up, warm up, time the K
+steps, write the outputs (``--dump-outputs``), print the JSON line.  Everything else this file
+measures - the accuracy runs, the all-reduce replay time of a multi-GPU run, ``--force-dp`` -
+runs only with ``--full``.
 
 Timing: W untimed warm-up steps, then more untimed steps until at least ``--min-warmup-s`` of
 warm-up has elapsed (a fresh box starts at low clocks: 20 timed steps are only ~5 ms), then
@@ -21,7 +27,16 @@ EXACTLY K steps bracketed by barrier + device synchronize on every rank; the max
 reported.  Weak scaling by default (``--npts`` per GPU); ``--global-npts`` fixes the total
 (strong scaling, e.g. the reference's AC-dist-new config: 500,000 points, examples/AC-dist-new.py).
 
-Accuracy half of the metric (after the timed region, ``--acc-seeds``, at every GPU count): the
+``--dump-outputs DIR`` writes what the timed steps left behind, as a caller of ``AdamEngine.run``
+finds it after the last one: ``DIR/params.npy`` (theta), ``DIR/lambda_<i>.npy`` (SA weights, and
+the coefficients of the discovery problem after them), ``DIR/loss.npy`` (the last step's history
+row: total loss, then every term), float32, rank 0's tensors, at most 64 MB in all (a fixed seeded
+sample of a larger tensor).  The warm-up runs for a time, not a count, so with this option
+parameters, SA weights and optimizer state are put back to their seeded initial values after the
+warm-up (outside the timed region): the K timed steps then start from the same inputs in every
+run, and two builds can be compared output for output.
+
+Accuracy half of the metric (``--full``; after the timed region, ``--acc-seeds``, at every GPU count): the
 reference AC-SA schedule (examples/AC-SA.py:64-88: Adam 10k + L-BFGS 10k; Adam in the bench
 precision, L-BFGS in ``newton_precision`` bf16x3) from scratch per seed on its 50k points -
 sharded over the ranks, with their SA weights, at ``--gpus N`` - relative L2 on data/AC.mat, wall
@@ -240,9 +255,30 @@ def l2_on_ac_grid(model):
     return find_L2_error(u_pred, u_star)
 
 
-def time_steps(eng, ctx, device, steps, warmup, min_warmup_s):
+def engine_state(eng):
+    """Every tensor an Adam step reads and updates: parameters, SA weights (and discovery
+    coefficients), their Adam moments and the optimizers' step counters."""
+    return list(eng.wrt) + [t for ms in eng.moments for mv in ms for t in mv] + list(eng.counters)
+
+
+def dump_outputs(out_dir, eng, model, budget=64 << 20):
+    """``--dump-outputs``: what the last timed step left, as float32 ``.npy`` files (module docstring)."""
+    os.makedirs(out_dir, exist_ok=True)
+    row = int(model._state["epoch_host"]) - 1
+    arrays = {"params": eng.wrt[0], "loss": model._state["hist"][row]}
+    arrays.update({f"lambda_{i}": t for i, t in enumerate(eng.wrt[1:])})
+    share = budget // 4 // len(arrays)     # float32 elements per file
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1).to(torch.float32).cpu().numpy()
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def time_steps(eng, ctx, device, steps, warmup, min_warmup_s, before_timed=None):
     """Warm up (>= ``warmup`` steps and >= ``min_warmup_s`` seconds), then time exactly ``steps``
-    steps between barrier + synchronize pairs; returns (seconds, warm-up steps run, warm-up s)."""
+    steps between barrier + synchronize pairs; returns (seconds, warm-up steps run, warm-up s).
+    ``before_timed()`` runs after the warm-up, outside the timed region."""
     def sync():
         if device.type == "cuda":
             torch.cuda.synchronize(device)
@@ -267,6 +303,8 @@ def time_steps(eng, ctx, device, steps, warmup, min_warmup_s):
     n_warm += K + 1
     sync()
     warm_s = time.perf_counter() - t_w
+    if before_timed is not None:
+        before_timed()
     ctx.barrier()
     sync()
     t0 = time.perf_counter()
@@ -346,9 +384,10 @@ def accuracy_runs(seeds, device, backend, precision, newton_precision, iters, ne
             c1, c2 = discovery_c1(m.vars[0]), float(m.vars[1].detach())
             res = {"seed": sd, "c1": c1, "c2": c2, "c1_rel_err": abs(c1 - 1e-4) / 1e-4, "c2_rel_err": abs(c2 - 5.0) / 5.0}
         elif problem == "ac-dist":
-            m.fit(tf_iter=AC_DIST_ADAM)
+            n_adam = min(AC_DIST_ADAM, iters)   # the reference's 1001 unless --acc-iters asks for fewer
+            m.fit(tf_iter=n_adam)
             a1 = m.fit_info.get("adam", {}).get("wall_s", 0.0)
-            m.fit(tf_iter=AC_DIST_ADAM)
+            m.fit(tf_iter=n_adam)
             m.fit_info.setdefault("adam", {})["wall_s"] = a1 + m.fit_info.get("adam", {}).get("wall_s", 0.0)
             res = {"seed": sd, "l2": float(l2_on_ac_grid(m))}
         else:
@@ -412,10 +451,17 @@ def main(argv=None):
     ap.add_argument("--layers", default=None,
                     help="network layer sizes (default: the problem's reference net; widths 129-256 run "
                          "the fused kernels in bf16, wider nets / other precisions the layer-wise engine)")
-    ap.add_argument("--no-l2", action="store_true", help="skip the accuracy runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures: the accuracy "
+                         "runs (unless --no-l2), the all-reduce replay time of a multi-GPU run, --force-dp")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (parameters, SA weights, loss row) as "
+                         "DIR/<name>.npy; the timed steps then start from the seeded initial state")
+    ap.add_argument("--no-l2", action="store_true", help="--full: skip the accuracy runs")
     ap.add_argument("--acc-seeds", type=int, nargs="*", default=[0, 1, 2],
                     help="seeds of the full-schedule accuracy runs (under data parallelism at --gpus N)")
-    ap.add_argument("--acc-iters", type=int, default=10000)
+    ap.add_argument("--acc-iters", type=int, default=10000,
+                    help="Adam steps of the accuracy runs (ac-dist: of each of its two fits, 1001 at most)")
     ap.add_argument("--acc-npts", type=int, default=None,
                     help="points of the accuracy runs (default: the reference schedule's, 50k / AC-dist 500k)")
     ap.add_argument("--acc-newton", type=int, default=None,
@@ -428,7 +474,7 @@ def main(argv=None):
     ap.add_argument("--lbfgs-stop", default=None, choices=["fixed", "legacy"],
                     help="L-BFGS function-change test (default: the library's, legacy = the reference's)")
     ap.add_argument("--force-dp", action="store_true",
-                    help="also time the DP step at world 1 (RCCL process group, single GPU only)")
+                    help="--full: also time the DP step at world 1 (RCCL process group, single GPU only)")
     ap.add_argument("--precision", default="bf16", choices=["bf16x3", "bf16", "fp32"],
                     help="GEMM precision of the HIP jet kernels (bf16x3 = split-bf16 MFMA, fp32 accumulate; "
                          "bf16 = bf16 x bf16 MFMA, fp32 accumulate)")
@@ -436,6 +482,8 @@ def main(argv=None):
                     help="discovery: the reference's raw c1 = v from 0 (default) or c1 = exp(v) from v = -6 "
                          "(not the reference's parametrization)")
     args = ap.parse_args(argv)
+    if args.force_dp and not args.full:
+        ap.error("--force-dp is an extra measurement: add --full")
     global DISCOVERY_C1
     DISCOVERY_C1 = args.c1_param
 
@@ -478,14 +526,24 @@ def main(argv=None):
                           newton_precision=args.newton_precision)
     eng = get_engine(model, args.warmup + args.steps + 2)
     backend = backend_of(model)
-    elapsed, n_warm, warm_s = time_steps(eng, ctx, device, args.steps, args.warmup, args.min_warmup_s)
+    reset = None
+    if args.dump_outputs:
+        init = [(t, t.detach().clone()) for t in engine_state(eng)]
+
+        def reset():
+            with torch.no_grad():
+                for t, t0 in init:
+                    t.copy_(t0)
+    elapsed, n_warm, warm_s = time_steps(eng, ctx, device, args.steps, args.warmup, args.min_warmup_s, reset)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, eng, model)
     steps_per_graph = eng._unroll()
     loss = float(model._state["hist"][int(model._state["epoch_host"]) - 1, 0])
     total_steps = int(model._state["epoch_host"])
     pts_per_s = n_glob * args.steps / elapsed
     rank_ms = getattr(time_steps, "rank_ms", None)
     ar = None
-    if dist:
+    if dist and args.full:
         bucket = getattr(eng, "_dp_buf", None)
         n_bucket = bucket.numel() if bucket is not None else model.u_model.flat.numel() + 8
         try:
@@ -495,7 +553,7 @@ def main(argv=None):
     del eng, model
 
     acc, acc_err = None, None
-    if not args.no_l2 and args.acc_seeds and acc_ok:
+    if args.full and not args.no_l2 and args.acc_seeds and acc_ok:
         try:
             acc = accuracy_runs(args.acc_seeds, device, args.backend, args.precision, args.newton_precision,
                                 args.acc_iters, args.acc_newton, args.lbfgs_stop, problem=args.problem,
@@ -504,7 +562,7 @@ def main(argv=None):
         except Exception as e:  # pragma: no cover - reported, never hides the throughput number
             acc_err = f"{type(e).__name__}: {e}"
     dp = None
-    if args.force_dp and world == 1 and device.type == "cuda" and args.problem == "ac-sa":
+    if args.full and args.force_dp and world == 1 and device.type == "cuda" and args.problem == "ac-sa":
         try:
             dp = forced_dp_timing(n_glob, args.backend, device, args.precision, args.steps, args.warmup,
                                   args.min_warmup_s)
@@ -554,7 +612,7 @@ def main(argv=None):
             rec["l2_full_schedule_seeds"] = [a["l2"] for a in acc]
             on = f"on {world} GPUs (data parallel, points and SA weights sharded)" if world > 1 else "on 1 GPU"
             if args.problem == "ac-dist":
-                rec["accuracy_schedule"] = (f"Adam {AC_DIST_ADAM} x 2 ({args.precision}), N_f {args.acc_npts or spec['npts']}, "
+                rec["accuracy_schedule"] = (f"Adam {min(AC_DIST_ADAM, args.acc_iters)} x 2 ({args.precision}), N_f {args.acc_npts or spec['npts']}, "
                                             f"reference examples/AC-dist-new.py, {on}; median over seeds "
                                             f"{args.acc_seeds}")
             else:

@@ -56,6 +56,35 @@ def test_bench_single_process_json():
 
 
 @pytest.mark.timeout(300)
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no ``--full``, no ``--no-l2``) times its steps and nothing else: no accuracy
+    runs in the JSON line.  ``--dump-outputs`` writes the last timed step's parameters, SA weights
+    and loss row as float32 ``.npy``; two runs with the same arguments start their timed steps from
+    the same inputs (the time-based warm-up runs a different number of steps each time), so the
+    CPU path, which has no atomics, reproduces them bit for bit."""
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--npts", "512", "--min-warmup-s", "0.05"]
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(d)],
+                           capture_output=True, text=True, env=_env(), timeout=280, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = _last_json(r.stdout)
+        _check(rec, 1)
+        assert not any(k in rec for k in ("l2_full_schedule", "accuracy_schedule", "time_to_solution_s", "forced_dp"))
+        outs.append({p.name: np.load(p) for p in sorted(d.glob("*.npy"))})
+        assert sorted(outs[-1]) == ["lambda_0.npy", "lambda_1.npy", "loss.npy", "params.npy"]
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in outs[-1].values())
+        assert outs[-1]["lambda_0.npy"].shape == (512,) and outs[-1]["loss.npy"][0] == pytest.approx(rec["loss_after"])
+    for name in outs[0]:
+        assert np.array_equal(outs[0][name], outs[1][name]), name
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dp"] + args, capture_output=True,
+                       text=True, env=_env(), timeout=280, cwd=ROOT)
+    assert r.returncode == 2 and "--full" in r.stderr      # extras are refused without --full, never dropped
+
+
+@pytest.mark.timeout(300)
 def test_bench_two_ranks_gloo_json():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
@@ -71,8 +100,8 @@ def test_bench_two_ranks_gloo_json():
 def test_bench_self_launch_two_ranks_json():
     """``python bench.py --gpus 2`` with no launcher: bench.py re-runs itself as 2 ranks (child
     processes under torch.distributed.run) and relays rank 0's single JSON line."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL, capture_output=True,
-                       text=True, env=_env(), timeout=280, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full"] + SMALL,
+                       capture_output=True, text=True, env=_env(), timeout=280, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _last_json(r.stdout)
     _check(rec, 2)
@@ -142,7 +171,7 @@ def test_bench_accuracy_under_dp_two_ranks(problem):
     """at --gpus N the accuracy schedule runs under data parallelism (points and
     SA weights sharded) and rank 0's JSON carries its L2 next to the throughput (tiny CPU sizes)."""
     args = ["--steps", "2", "--warmup", "1", "--min-warmup-s", "0.01", "--problem", problem, "--gpus", "2",
-            "--acc-seeds", "0", "--acc-iters", "3", "--acc-newton", "3", "--acc-npts", "512"]
+            "--full", "--acc-seeds", "0", "--acc-iters", "3", "--acc-newton", "3", "--acc-npts", "512"]
     args += ["--npts", "256"] if problem == "ac-sa" else ["--global-npts", "512"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
                        env=_env(), timeout=280, cwd=ROOT)

@@ -215,8 +215,8 @@ def test_bench_self_launch_two_ranks_share_gpu(problem):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.update(TDQ_DIST_BACKEND="gloo", PYTHONPATH=root + os.pathsep + env.get("PYTHONPATH", ""))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "4",
-           "--npts", "8192", "--no-l2", "--min-warmup-s", "0.2", "--problem", problem]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "20",
+           "--warmup", "4", "--npts", "8192", "--no-l2", "--min-warmup-s", "0.2", "--problem", problem]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=280, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
