@@ -658,7 +658,8 @@ __global__ void __launch_bounds__(256) lbfgs_axpy_kernel(float* __restrict__ x, 
 //                     trajectory is bit-identical to the five-launch path.  With a weight-image
 //                     target (the split-bf16 objective's scratch) every new x element is also
 //                     scattered into the next evaluation's bf16 hi / lo A images and fp32 aux
-//                     image, so the objective runs without its pack launch.
+//                     image, so the objective runs without its pack launch.  (Plain stores: the
+//                     undo of a stop restores x only, the images are then stale - see the tail.)
 // The order of every reduction is the five-launch path's: same values, bit for bit.
 __global__ void __launch_bounds__(256) lbfgs_dots_logic_kernel(const float* __restrict__ fg,
                                                                const float* __restrict__ g_old,
@@ -796,11 +797,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) l
   __syncthreads();
   if (stop) {  // undo the speculative step: x stays where the reference leaves it
     // every block stored x_prev / x write-through and drained them before its ticket (vmcnt(0)
-    // above): sc1 loads see them, sc1 stores overwrite the speculative x in memory
+    // above): sc1 loads see them, sc1 stores overwrite the speculative x in memory.
+    // The weight images are NOT restored: every block scattered the speculative x into them with
+    // plain stores, so their dirty lines sit in the L2 of whichever XCD ran the block and reach
+    // memory at kernel end in no defined order - a restore from this one block could land before
+    // or after them (MI355X_MICROARCH.md: plain stores KEEP the line in the storing XCD's L2;
+    // the hand-off table's rows all need every store of the handed-off bytes sc1 and drained).
+    // Write-through image stores would repair that, but they are 2-byte scatters - one fabric
+    // write each, ~12.5x a 16-B store per byte (same table) - paid on every step for a stop that
+    // ends the run.  So the images keep the speculative weights and are stale after a reason-5
+    // stop (DeviceLBFGS.images_stale); the next run's first evaluation packs them from x.
     for (int j = threadIdx.x; j < c.p; j += 256) {
       const float xo = __hip_atomic_load(&x_prev[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&x[j], xo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (ti.fimg != nullptr) scatter_param(xo, j, ti);  // (the images' lines: one block, kernel end)
     }
   }
 }

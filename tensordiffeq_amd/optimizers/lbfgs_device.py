@@ -230,6 +230,7 @@ class DeviceLBFGS:
             st[ACTIVE] = 0.0
             st[REASON] = float(reason)
             st[PUSHED] = 0.0
+            st[SLOT] = -1.0
             return
         n_iter += 1
         st[NITER] = float(n_iter)
@@ -299,6 +300,14 @@ class DeviceLBFGS:
     def reason(self):
         return REASONS.get(int(self.st[REASON]), "?")
 
+    @property
+    def images_stale(self):
+        """The weight images of ``img_target`` no longer match ``x``: a "no descent direction" stop
+        undoes the speculative step in ``x`` only (csrc/lbfgs.hip ``lbfgs_dir_step_kernel``), so the
+        images still hold the step that was not taken.  Pack them before the next evaluation
+        without a pack launch (:func:`minimize` always packs in its first evaluation)."""
+        return self.img_target is not None and int(self.st[REASON]) == 5
+
     def history(self):
         """Loss after every evaluation (index 0 = initial point)."""
         if self.fhist is None:
@@ -319,7 +328,9 @@ def minimize(evaluate, x, max_iter, m=50, lr=0.8, tol_fun=1e-12, tol_x=1e-12, al
     ``fhist``); ``x`` is left at the LAST iterate - callers restore ``best_x``.  ``stop``: the
     function-change test, see :data:`STOP_MODES`.  ``images``: ``(img_target, evaluate_nopack)``
     of a one-launch objective (``LossGradEngine.image_target``) - the fused update writes the
-    next x's weight images and every evaluation after the first skips its pack launch."""
+    next x's weight images and every evaluation after the first skips its pack launch.  After a
+    "no descent direction" stop the images hold the step that was undone in ``x``
+    (:attr:`DeviceLBFGS.images_stale`); only ``evaluate``, which packs, may be called after that."""
     opt = DeviceLBFGS(x, m=m, max_iter=max_iter, lr=lr, tol_fun=tol_fun, tol_x=tol_x, stop=stop,
                       img_target=images[0] if images is not None else None)
     graph_ok = x.is_cuda and opt.native

@@ -301,6 +301,30 @@ def test_fused_update_descent_stop_restores_x(monkeypatch):
         outs.append((x.clone(), opt.reason, opt.n_iter))
     assert outs[0][1] == outs[1][1] == LD.REASONS[5]
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][0], torch.ones(5000, device="cuda"))
+    # with a weight-image target the undo restores x only (the speculative step was scattered into
+    # the images with plain stores from every block: lbfgs_dir_step_kernel): the images are flagged
+    # stale, and a pack from x - the next run's first evaluation - is what brings them back
+    from tensordiffeq_amd.jet import JetPlan
+    from tensordiffeq_amd.models.networks import TanhMLP
+    from tensordiffeq_amd.ops import jet_hip
+    monkeypatch.setenv("TDQ_LBFGS_FUSED", "1")
+    net = TanhMLP([2, 128, 128, 128, 128, 1], device="cuda")
+    x = net.flat.detach().clone().contiguous()
+    x0 = x.clone()
+    X = torch.rand(512, 2, device="cuda")
+    _, saved = jet_hip.alloc_forward(X, x, net, JetPlan([(0,), (1,), (0, 0)], 2), "bf16x3")
+    saved[2].zero_()
+    jet_hip.pack_images(saved)
+    packed = saved[2].clone()
+    evaluate = lambda: torch.cat([torch.full((x.numel(),), 1e-9, device="cuda"),
+                                  torch.ones(1, device="cuda")]).contiguous()
+    opt = LD.minimize(evaluate, x, 10, use_graph=False, images=(jet_hip.img_target(saved), evaluate))
+    torch.cuda.synchronize()
+    assert opt.fused and opt.reason == LD.REASONS[5] and torch.equal(x, x0)
+    assert opt.images_stale
+    jet_hip.pack_images(saved)
+    torch.cuda.synchronize()
+    assert torch.equal(saved[2].view(torch.int32), packed.view(torch.int32))
 
 
 @pytest.mark.gpu
