@@ -593,13 +593,12 @@ int tdq_dp_tail_b_bf3(float* scratch, int N, int d_in, const int* widths, int d_
 
 // One launch of a run-time compiled fused training step (ops/fused_step.py; lo = 0: the bf16 step of
 // csrc/jet_fused.h, 32-point tiles; lo = 1: the bf16x3 objective of csrc/jet_fused3.h, 16-point
-// tiles): forward -> loss -> backward over the points [p_lo, N), G workgroups, gradient-slab rows
-// srow.., loss-partial rows prow.. (nacc floats each)
+// tiles): forward -> loss -> backward over the N points, G workgroups, one gradient-slab row each
+// from row 0, loss-partial rows prow.. (nacc floats each)
 int tdq_fused_step_launch(void* func, const float* X, float* scratch, float* work, int N, int d_in, const int* widths,
-                          int d_out, int n_hidden, int S, const int* spec, int p_lo, int srow, int G, const void* lptrs,
+                          int d_out, int n_hidden, int S, const int* spec, int G, const void* lptrs,
                           float* lpart, int prow, int nacc, int lo, void* stream) {
-  if (func == nullptr || N <= 0 || p_lo < 0 || p_lo >= N || G < 1 || srow < 0 || prow < 0 || nacc < 1 || lo < 0 ||
-      lo > 1)
+  if (func == nullptr || N <= 0 || G < 1 || prow < 0 || nacc < 1 || lo < 0 || lo > 1)
     return (int)hipErrorInvalidValue;
   NetDims d;
   if (!make_dims(d, d_in, widths, 0, d_out, n_hidden)) return (int)hipErrorInvalidValue;
@@ -609,7 +608,7 @@ int tdq_fused_step_launch(void* func, const float* X, float* scratch, float* wor
     return (int)hipErrorInvalidValue;
   const int PT = lo ? FZ3_PT : FZ_PT;
   // at most one workgroup per tile: every workgroup owns at least one tile
-  if (G > (N - p_lo + PT - 1) / PT) return (int)hipErrorInvalidValue;
+  if (G > (N + PT - 1) / PT) return (int)hipErrorInvalidValue;
   JetSpec sp;
   if (spec_nso(S, spec) < 0 || !make_spec(S, spec, sp)) return (int)hipErrorInvalidValue;
   float *img, *bimg, *aux;
@@ -622,9 +621,7 @@ int tdq_fused_step_launch(void* func, const float* X, float* scratch, float* wor
   P.slab = work;
   P.N = N;
   P.Pst = slab_stride(param_count(d));
-  P.ntiles = (N - p_lo + PT - 1) / PT;
-  P.p_lo = p_lo;
-  P.srow = srow;
+  P.ntiles = (N + PT - 1) / PT;
   P.d = d;
   P.sp = sp;
   P.lptrs = reinterpret_cast<const FzLossPtrs*>(lptrs);

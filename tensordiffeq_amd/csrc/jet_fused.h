@@ -26,7 +26,9 @@
 // Removed after measurement (tools/patches/fused_step_experiments_REMOVED.patch, A/B notes there):
 // the MODE 0 / 1 forward-only and backward-only persistent launches (TDQ_FUSED=1), the dynamic
 // tile queue (TDQ_FS_DYNAMIC), the loss inputs prefetched a tile ahead (TDQ_FS_PREFETCH), the
-// cheap tanh in the hidden layers (FZ_CHEAP_TANH) and the weight-lo "bf16w" objective (WLO).
+// cheap tanh in the hidden layers (FZ_CHEAP_TANH) and the weight-lo "bf16w" objective (WLO);
+// the residual-only layout of mixed programs, its point and slab-row offsets
+// (tools/patches/fused_step_residual_layout_REMOVED.patch).
 // The L-BFGS objective in bf16x3 runs the 16-point-tile kernel of jet_fused3.h.
 // Reference behaviour: the nested tf.gradients of the PDE residual and its tape.gradient
 // (tensordiffeq/models.py:116-225, fit.py:125-147).
@@ -250,10 +252,8 @@ struct FzParams {
   const float* aux;
   const bf16x8* fimg;   // forward A image ([out][in] k order)
   const bf16x8* bimg;   // backward A image ([in][out])
-  float* slab;          // gradient-slab rows srow + blockIdx.x
-  int N, Pst, ntiles;
-  int p_lo;             // the tiles cover points [p_lo, N)
-  int srow;
+  float* slab;          // gradient-slab row blockIdx.x
+  int N, Pst, ntiles;   // the tiles cover points [0, N)
   NetDims d;
   JetSpec sp;
   // the loss program's pointer table (the generated loss maps a point to its group)
@@ -338,7 +338,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   static_assert(FZ_PT * TDQ_MAXD + FZ_PT <= 64 * FZ_WAVES, "one element per thread");
   float xpre = 0.f;
   auto fetch = [&](int tt) {
-    const int pb = P.p_lo + tt * FZ_PT;
+    const int pb = tt * FZ_PT;
     if (tid < FZ_PT * TDQ_MAXD) {
       const int pt = tid / TDQ_MAXD, j = tid - pt * TDQ_MAXD;
       const int n = min(pb + pt, N - 1);
@@ -385,7 +385,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   int t = t0;
   TDQ_TS(0);
   while (t < t1) {
-    const int pb = P.p_lo + t * FZ_PT;
+    const int pb = t * FZ_PT;
     asm volatile("" : "+s"(Wimg), "+s"(Kimg));
     __syncthreads();  // the previous tile's readers of xs / ubs / images are done (and aux / part set)
     if (tid < FZ_PT * TDQ_MAXD) xs[tid] = xpre;
@@ -593,7 +593,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   TDQ_TS(62);
 
   // ---- this workgroup's gradient-slab row (bf16) ---------------------------------------------
-  __bf16* gs = reinterpret_cast<__bf16*>(P.slab) + (size_t)(P.srow + gi) * Pst;
+  __bf16* gs = reinterpret_cast<__bf16*>(P.slab) + (size_t)gi * Pst;
 #pragma unroll
   for (int ly = 1; ly <= LM; ++ly) {
     const int voff = ((16 * r0 + 4 * g) * W + 16 * c0 + p) * 2;

@@ -195,7 +195,7 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
 
   float xpre = 0.f;
   auto fetch = [&](int tt) {
-    const int pb = P.p_lo + tt * PT;
+    const int pb = tt * PT;
     if (tid < PT * TDQ_MAXD) {
       const int pt = tid / TDQ_MAXD, j = tid - pt * TDQ_MAXD;
       const int n = min(pb + pt, N - 1);
@@ -248,7 +248,7 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
   Fz3W<WT> wf;  // a GEMM's weight fragments
   TDQ_TS(0);
   while (t < t1) {
-    const int pb = P.p_lo + t * PT;
+    const int pb = t * PT;
     asm volatile("" : "+s"(Wimg), "+s"(Kimg));
     __syncthreads();  // the previous tile's readers of xs / ubs / images are done (and aux / part set)
     if (tid < PT * TDQ_MAXD) xs[tid] = xpre;
@@ -418,7 +418,7 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
   TDQ_TS(62);
 
   // ---- this workgroup's gradient-slab row (fp32) ---------------------------------------------
-  float* gs = P.slab + (size_t)(P.srow + gi) * Pst;
+  float* gs = P.slab + (size_t)gi * Pst;
 #pragma unroll
   for (int ly = 1; ly <= LM; ++ly) {
     float* row = gs + off_layer(d, ly) + (16 * r0 + 4 * g) * W + 16 * c0 + p;

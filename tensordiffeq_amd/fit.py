@@ -93,6 +93,11 @@ class AdamEngine:
         self.wrt = [t for g in self.groups for t in g.tensors]
         self.bind = bind if bind is not None else default_bind(len(self.lambdas))
         self.red_idx = [i for i, r in enumerate(r for g in self.groups for r in g.reduce) if r]
+        self.points = PointPass(program, self.flat)
+        # created lazily: the fused-loss gradient map, the fused tail's theta gradient, the DP bucket,
+        # the optimizers' signature, the K-step graph, the captured step's forward scratch
+        self._fsrc = self._grad = self._dp_buf = self._sig = self.graph_k = self._graph_saved = None
+        self._sum_terms = False
         self._bind_opts()
         self._ensure_hist(n_steps_hint)
 
@@ -144,7 +149,7 @@ class AdamEngine:
 
     def _fused_grads(self, fop, gflat, dlam, dscal):
         """Per-wrt-tensor gradients from the fused-loss outputs and the flat theta gradient."""
-        if getattr(self, "_fsrc", None) is None:
+        if self._fsrc is None:
             self._fsrc = self._fused_map(fop)
         grads = []
         for (kind, k), w in zip(self._fsrc, self.wrt):
@@ -221,7 +226,7 @@ class AdamEngine:
             torch.stack([t.float().reshape(()) for t in terms]) if len(terms)
             else torch.zeros(0, device=self.device))
         fused.step_book(loss, tv.reshape(-1).float().contiguous(), st, self.counters,
-                        sum_terms=getattr(self, "_sum_terms", False))
+                        sum_terms=self._sum_terms)
 
     def _opt_groups(self, grads):
         """``fused.adam_multi_opts`` rows: each group with its optimizer's counter and
@@ -250,49 +255,17 @@ class AdamEngine:
 
     # ------------------------------------------------------------ fused step tail ------
     def _tail_eligible(self):
-        """Step on the split-bf16 jet kernels with the fused loss: single-process, the end of the
-        step runs as two launches (csrc/jet_bf3.hip ``tdq_step_tail_bf3``); under DP the captured
-        halves use ``tdq_dp_tail_a_bf3`` / ``tdq_dp_tail_b_bf3`` around the all-reduce."""
-        if getattr(self, "_tail_ok", None) is not None:
-            return self._tail_ok
-        ok = False
-        fop = getattr(self.program, "fused_op", None)
-        if (os.environ.get("TDQ_FUSED_TAIL", "1") != "0" and fop is not None
-                and self.device.type == "cuda" and self.groups[0].tensors[0] is self.flat):
-            from .ops import _lib, jet_hip
-            from .ops.jet_mlp import hip_config
-            prog = self.program
-            try:
-                ok = jet_hip.is_split_bf16(hip_config(prog.net, prog.plan, prog.precision)) and _lib.available()
-            except (ValueError, AttributeError):
-                ok = False
+        """Step on the split-bf16 jet kernels with the fused loss (:class:`PointPass`) and one
+        Adam launch over every group: single-process, the end of the step runs as two launches
+        (csrc/jet_bf3.hip ``tdq_step_tail_bf3``); under DP the captured halves use
+        ``tdq_dp_tail_a_bf3`` / ``tdq_dp_tail_b_bf3`` around the all-reduce."""
+        if self._tail_ok is None:
+            ok = self.points.eligible and self.groups[0].tensors[0] is self.flat
             if ok:
                 probe = [(w, w, m, v, 1.0) for w, (m, v) in zip(self.wrt, (mv for ms in self.moments for mv in ms))]
                 ok = fused.group_array([(probe, self.counters[0], 0.0, 0.0, 0.0, 0.0)]) is not None
-        self._tail_ok = ok
-        return ok
-
-    def _step_buffers(self):
-        """Jets, forward scratch (saved activations + weight images), gradient slabs and the
-        theta gradient of the fused-tail step, allocated once per engine."""
-        if getattr(self, "_bufs", None) is None:
-            from .ops import jet_hip
-            prog = self.program
-            J, saved = jet_hip.alloc_forward(prog.X_all, self.flat, prog.net, prog.plan, prog.precision,
-                                             rows=prog.fused_op.fl.n_streams)
-            self._bufs = (J, saved, jet_hip.alloc_backward(saved), torch.empty_like(self.flat))
-        return self._bufs
-
-    def _fused_step(self):
-        """The one-launch residual step (ops/fused_step.py) or None."""
-        from .ops import fused_step
-        return fused_step.for_program(self.program)
-
-    def _point_ranges(self, fop):
-        if getattr(self, "_ranges", 0) == 0:
-            self._ranges = point_ranges(self.program, fop)
-            self._streams = [torch.cuda.Stream(device=self.device) for _ in (self._ranges or ())]
-        return self._ranges
+            self._tail_ok = ok
+        return self._tail_ok
 
     def _tail_step(self, in_graph):
         """One Adam step ending in the fused tail.  ``in_graph``: the step is being captured, so
@@ -309,8 +282,10 @@ class AdamEngine:
                              f"{self.flat.numel()}")
         # persistent buffers: every captured step (the 1-step and the K-step graph) reads the weight
         # images the previous step's tail wrote into this one scratch
-        J, saved, work, grad = self._step_buffers()
-        pre, kw = self._run_points(J, saved, work, pack=not in_graph)
+        saved, work, pre, kw = self.points.run(pack=not in_graph)
+        if self._grad is None:
+            self._grad = torch.empty_like(self.flat)
+        grad = self._grad
         grads = self._fused_grads(fop, grad, fop.dlam, fop.dscal)
         packed = fused.group_array(self._opt_groups(grads))
         if packed is None:  # gradient tensors the single launch cannot take: reduce, then Adam
@@ -321,20 +296,6 @@ class AdamEngine:
                           write_images=in_graph, c_first=pre, gextra=hi.grad if hi is not None else None, **kw)
         self._tail_saved = saved
         return fop.total
-
-    def _run_points(self, J, saved, work, pack):
-        """Gradient slabs + loss partials of every point: the fused residual step beside the
-        boundary chain, else the point ranges' forward -> loss -> backward chains.  Returns
-        ``(first slab chunk of the tail, tail keyword arguments)``."""
-        prog, fop = self.program, self.program.fused_op
-        fs = self._fused_step()
-        if fs is not None:
-            fs.run(saved, J, work, self.flat, pack=pack)
-            return 0, fs.tail_kw()
-        rng = self._point_ranges(fop) or [(0, prog.X_all.shape[0], 0, fop.n_blocks)]
-        pre = prereduce_chunk(prog, rng)
-        run_ranges(prog, fop, self.flat, rng, self._streams, pack=pack, bufs=(J, saved, work), prereduce=pre)
-        return pre, {}
 
     def _dp_tail_phase_b(self, loss, grads, terms):
         """DP graph half after the all-reduce: bookkeeping, then Adam + snapshot + weight images."""
@@ -368,7 +329,7 @@ class AdamEngine:
     # ---------------------------------------------------------------- graphs -------------
     def _capture(self):
         if self._tail_eligible():
-            self._fused_step()   # built (hipRTC compile + module load) outside any capture
+            self.points.fused_step()   # built (hipRTC compile + module load) outside any capture
         stream = torch.cuda.Stream(device=self.device)
         stream.wait_stream(torch.cuda.current_stream(self.device))
         split = self.dist.is_distributed
@@ -434,8 +395,7 @@ class AdamEngine:
         fop = prog.fused_op
         # persistent step buffers (as in _tail_step): the 1-step and the K-step graph read the
         # weight images that the previous step's dp_tail_b wrote into this one scratch
-        J, saved, work, _ = self._step_buffers()
-        pre, kw = self._run_points(J, saved, work, pack=pack)
+        saved, work, pre, kw = self.points.run(pack=pack)
         n_p = self.flat.numel()
         red_idx = self.red_idx
         if not red_idx or red_idx[0] != 0:
@@ -443,7 +403,7 @@ class AdamEngine:
         others = [i for i in red_idx[1:]]
         sizes = [self.wrt[i].numel() for i in others]
         n_e, n_t = sum(sizes), fop.n_terms
-        buf = getattr(self, "_dp_buf", None)
+        buf = self._dp_buf
         if buf is None or buf.numel() != n_p + n_e + 1 + n_t:
             buf = self._dp_buf = torch.empty(n_p + n_e + 1 + n_t, dtype=torch.float32, device=self.device)
         grad_view = buf[:n_p]
@@ -509,7 +469,7 @@ class AdamEngine:
             return None
         opts = [g.get_opt() for g in self.groups]
         sig = [(o.learning_rate, o.beta_1, o.beta_2, o.epsilon) for o in opts]
-        if any(a is not b for a, b in zip(opts, self.opts)) or sig != getattr(self, "_sig", sig):
+        if any(a is not b for a, b in zip(opts, self.opts)) or self._sig not in (None, sig):
             self._bind_opts()
             self.graph_a = self.graph_b = None
             self.graph_k = None
@@ -524,7 +484,7 @@ class AdamEngine:
             done = 1
             if progress is not None and n_steps == 1:
                 progress(1, float(loss))
-        if use_graph and self.graph_a is not None and getattr(self, "_graph_saved", None) is not None \
+        if use_graph and self.graph_a is not None and self._graph_saved is not None \
                 and done < n_steps:
             # the captured step's forward reads weight images written by the previous replay's
             # tail: bring them up to date with the parameters as they are now
@@ -533,12 +493,12 @@ class AdamEngine:
         checked = int(st["epoch_host"]) - done
         K = self._unroll()
         if use_graph and self.graph_a is not None and K > 1 and n_steps - done >= K \
-                and getattr(self, "graph_k", None) is None:
+                and self.graph_k is None:
             self._capture_k(K)
         while done < n_steps:
             # K steps at once unless that would jump over a progress / NaN-check point
             next_log = (done // log_every + 1) * log_every if progress is not None else n_steps
-            if use_graph and K > 1 and getattr(self, "graph_k", None) is not None and n_steps - done >= K \
+            if use_graph and K > 1 and self.graph_k is not None and n_steps - done >= K \
                     and done + K <= next_log:
                 self.graph_k.replay()
                 loss = self.static_loss_k
@@ -734,6 +694,71 @@ def run_ranges(program, fop, flat, ranges, streams, pack=True, bufs=None, prered
     return saved, work
 
 
+class PointPass:
+    """Forward -> loss -> backward of every point on the split-bf16 jet kernels with the fused loss,
+    up to the gradient slabs and loss partials that the fused tail reduces (``jet_hip.step_tail`` /
+    ``dp_tail_a``): the one-launch fused step (ops/fused_step.py) if the program has one, else the
+    point ranges (:func:`run_ranges`).  ``persistent`` (the Adam step: every captured step reads the
+    weight images that the previous step's tail wrote): the ranges run on the persistent buffers
+    too, the whole set as one range when it has no cut.  Otherwise (the L-BFGS objective) only the
+    fused step does, and the ranges' buffers are allocated per evaluation."""
+
+    def __init__(self, program, flat, persistent=True):
+        self.program, self.flat, self.persistent = program, flat, persistent
+        self._bufs, self._ranges, self._streams = None, 0, []
+        fop = getattr(program, "fused_op", None)
+        self.eligible = False
+        if os.environ.get("TDQ_FUSED_TAIL", "1") != "0" and fop is not None and flat.is_cuda:
+            from .ops import _lib, jet_hip
+            from .ops.jet_mlp import hip_config
+            try:
+                self.eligible = bool(jet_hip.is_split_bf16(hip_config(program.net, program.plan, program.precision))
+                                     and _lib.available())
+            except (ValueError, AttributeError):
+                pass
+
+    def buffers(self):
+        """``(J, saved, work)``: jets, forward scratch (saved activations + weight images) and
+        gradient slabs, allocated once."""
+        if self._bufs is None:
+            from .ops import jet_hip
+            prog = self.program
+            J, saved = jet_hip.alloc_forward(prog.X_all, self.flat, prog.net, prog.plan, prog.precision,
+                                             rows=prog.fused_op.fl.n_streams)
+            self._bufs = (J, saved, jet_hip.alloc_backward(saved))
+        return self._bufs
+
+    def fused_step(self):
+        """The program's one-launch step (built on first use, outside any graph capture) or None."""
+        from .ops import fused_step
+        return fused_step.for_program(self.program)
+
+    def ranges(self):
+        if self._ranges == 0:
+            self._ranges = point_ranges(self.program, self.program.fused_op)
+            self._streams = [torch.cuda.Stream(device=self.flat.device) for _ in (self._ranges or ())]
+        return self._ranges
+
+    def run(self, pack=True):
+        """Gradient slabs + loss partials of every point.  Returns ``(saved, work, first slab chunk
+        of the tail, tail keyword arguments)`` - or ``None`` when not ``persistent`` and there is
+        neither a fused step nor a cut (the caller's single launches)."""
+        prog, fop = self.program, self.program.fused_op
+        fs = self.fused_step()
+        if fs is not None:
+            J, saved, work = self.buffers()
+            fs.run(saved, J, work, self.flat, pack=pack)
+            return saved, work, 0, fs.tail_kw()
+        rng = self.ranges()
+        if not rng and not self.persistent:
+            return None
+        rng = rng or [(0, prog.X_all.shape[0], 0, fop.n_blocks)]
+        pre = prereduce_chunk(prog, rng)
+        saved, work = run_ranges(prog, fop, self.flat, rng, self._streams, pack=pack or not self.persistent,
+                                 bufs=self.buffers() if self.persistent else None, prereduce=pre)
+        return saved, work, pre, {}
+
+
 class LossGradEngine:
     """``(f, g_theta)`` at a flat parameter vector (lambdas frozen, B15); DP all-reduced."""
 
@@ -745,72 +770,33 @@ class LossGradEngine:
         self.dist = solver.dist_ctx
         self.graph = None
         self.n_evals = 0
-
-    def _fused_tail(self):
-        """Split-bf16 kernels with the fused loss on a GPU: ``[grad | loss]`` is written in place
-        by the fused tail (slab pass 1 + loss reduction + total in one launch, slab pass 2 into the
-        buffer) instead of loss-reduce / total / slab / concatenate launches."""
-        ok = getattr(self, "_tail", None)
-        if ok is None:
-            ok = False
-            if os.environ.get("TDQ_FUSED_TAIL", "1") != "0" and self.flat.is_cuda:
-                from .ops import _lib, jet_hip
-                from .ops.jet_mlp import hip_config
-                prog = self.program
-                try:
-                    ok = jet_hip.is_split_bf16(hip_config(prog.net, prog.plan, prog.precision)) and _lib.available()
-                except (ValueError, AttributeError):
-                    ok = False
-            self._tail = ok
-        return ok
-
-    def _fused_bufs(self):
-        """Persistent forward / backward buffers of the one-launch objective."""
-        if getattr(self, "_fbufs", None) is None:
-            from .ops import jet_hip
-            prog = self.program
-            J, saved = jet_hip.alloc_forward(prog.X_all, self.flat, prog.net, prog.plan, prog.precision,
-                                             rows=prog.fused_op.fl.n_streams)
-            self._fbufs = (J, saved, jet_hip.alloc_backward(saved))
-        return self._fbufs
+        self.points = PointPass(program, self.flat, persistent=False)
 
     def image_target(self):
         """``(img_target, evaluate_fg without the pack launch)`` when the objective is the
         one-launch fused step (its weight images can be written by the optimizer's own update
         kernel, csrc/lbfgs.hip), else ``None``."""
-        fop = getattr(self.program, "fused_op", None)
-        if fop is None or not self._fused_tail() or getattr(self.program, "hi_op", None) is not None:
+        pp = self.points
+        if not pp.eligible or getattr(self.program, "hi_op", None) is not None or pp.fused_step() is None:
             return None
-        from .ops import fused_step, jet_hip
-        if fused_step.for_program(self.program) is None:
-            return None
-        return jet_hip.img_target(self._fused_bufs()[1]), (lambda: self._body(pack=False))
+        from .ops import jet_hip
+        return jet_hip.img_target(pp.buffers()[1]), (lambda: self._body(pack=False))
 
     def _body(self, pack=True):
         fop = getattr(self.program, "fused_op", None)
         if fop is not None:
             from .ops import jet_hip
             prog = self.program
-            if self._fused_tail():
+            if self.points.eligible:
+                # ``[grad | loss]`` written in place by the fused tail (slab pass 1 + loss reduction +
+                # total in one launch, slab pass 2 into the buffer)
                 fg = torch.empty(self.flat.numel() + 1, dtype=torch.float32, device=self.flat.device)
-                if getattr(self, "_ranges", 0) == 0:
-                    self._ranges = point_ranges(prog, fop)
-                    self._streams = [torch.cuda.Stream(device=self.flat.device) for _ in (self._ranges or ())]
                 hi = prog.hi_op
                 gx = hi.grad if hi is not None else None
-                from .ops import fused_step
-                # the one-launch objective (bf16: jet_fused.h, bf16x3: jet_fused3.h) on persistent
-                # buffers (the image target of the device L-BFGS points into their scratch)
-                fs = fused_step.for_program(prog)
-                if fs is not None:
-                    J, saved, work = self._fused_bufs()
-                    fs.run(saved, J, work, self.flat, pack=pack)
-                    jet_hip.dp_tail_a(saved, work, fg[:-1], fop, total=fg[-1:], gextra=gx, **fs.tail_kw())
-                    return fg
-                if self._ranges:
-                    pre = prereduce_chunk(prog, self._ranges)
-                    saved, work = run_ranges(prog, fop, self.flat, self._ranges, self._streams, prereduce=pre)
-                    jet_hip.dp_tail_a(saved, work, fg[:-1], fop, total=fg[-1:], c_first=pre, gextra=gx)
+                out = self.points.run(pack)
+                if out is not None:
+                    saved, work, pre, kw = out
+                    jet_hip.dp_tail_a(saved, work, fg[:-1], fop, total=fg[-1:], c_first=pre, gextra=gx, **kw)
                     return fg
                 J, saved = jet_hip.forward_raw(prog.X_all, self.flat, prog.net, prog.plan, prog.precision,
                                                rows=fop.fl.n_streams)

@@ -1,6 +1,6 @@
 """One-launch training step: forward -> loss -> backward of every point (hipRTC).
 
-The persistent point-tile kernel of ``csrc/jet_fused.h`` in its MODE 2 runs, per 32-point tile,
+The persistent point-tile kernel of ``csrc/jet_fused.h`` (the fused step) runs, per 32-point tile,
 the Taylor-jet forward of the network, the per-point loss of the fused loss program and its
 reverse sweep, and the recompute backward into the tile loop's register-resident weight gradient -
 so J and dJ never touch HBM and the step has no forward / loss / backward launch boundaries.  The
@@ -11,9 +11,9 @@ once per (network shape, loss program) and cached per process.  A step is then t
 plus the two-launch step tail (``jet_hip.step_tail`` / ``dp_tail_a``: slab reduction, loss
 bookkeeping, Adam).
 
-Programs with order-3/4 boundary streams (``jet_hi.hip``) run only their residual group fused and
-keep the boundary chain (high-order streams, saved-activation forward range, loss blocks, backward
-range) on a side stream beside it.
+Programs with order-3/4 boundary streams (``jet_hi.hip``) run every loss output on main-plan
+streams fused and keep the high-order outputs' chain (jet_hi forward, their loss blocks, jet_hi
+adjoint) on a side stream beside it.
 
 The reference's step is tensordiffeq/models.py:90-135 (``train_op_inner`` / ``update_loss``): a
 tape over the network, the residual and the boundary MSEs, then the optimizer.
@@ -26,6 +26,7 @@ the LDS images); its tail reduces fp32 slab rows.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import hashlib
 import os
@@ -302,6 +303,96 @@ def _compile(src, name="tdq_fused_step"):
     return _CACHE[k]
 
 
+def mixed_mode():
+    """``TDQ_FUSED_STEP_MIXED``: how a mixed program (order-3/4 boundary streams from jet_hi.hip)
+    runs.  ``split`` (default) - every loss output on main-plan streams runs in the fused launch (the
+    boundary groups' low-order outputs included), only the high-order outputs' chain (jet_hi
+    forward, their loss blocks, jet_hi adjoint) on a side stream; ``0`` - the point-range path.
+    MI355X, AC-baseline 50k: split 0.207 ms/step, point ranges 0.219-0.226 (AC-SA 0.168;
+    profiles/r5split3_*, r5acb_*).  The residual-only layout (``1``, 0.251 ms/step) was removed:
+    tools/patches/fused_step_residual_layout_REMOVED.patch."""
+    mode = os.environ.get("TDQ_FUSED_STEP_MIXED", "split")
+    if mode not in ("split", "0"):
+        raise ValueError(f"TDQ_FUSED_STEP_MIXED={mode!r}: accepted values are 'split' and '0'")
+    return mode
+
+
+def _mixed(prog):
+    return getattr(prog, "hi_op", None) is not None
+
+
+def fused_groups(prog, fop):
+    """``[(group, fused program, side program or None)]`` of the fused point set: every group whose
+    outputs read main-plan streams only runs whole in the fused launch; a mixed program's other
+    groups are split (:func:`fusion.split_by_streams`) - or the reason that does not apply (an output
+    reading main-plan and high-order streams together, or an SA weight read by both halves)."""
+    from .. import fusion
+    out = []
+    for gr in fop.fl.groups:
+        if all(s < prog.plan.S for (_, s) in gr.program.stream_regs):
+            out.append((gr, gr.program, None))
+            continue
+        sp = fusion.split_by_streams(fop.fl, gr, prog.plan.S)
+        if sp is None:
+            return "a loss output reads main-plan and high-order streams together (or both read one SA weight)"
+        out.append((gr, sp[0], sp[1]))
+    return out
+
+
+def point_layout(prog, groups):
+    """The fused point set of ``groups`` (:func:`fused_groups`): groups in program order, a periodic
+    group's two segments interleaved pair by pair, pair groups on even offsets.  Returns
+    ``(layout, idx, N)``: the ``[(program, start, n_slots, n)]`` of :func:`gen_loss`, the gather index
+    of the ``N`` points into ``prog.X_all`` (-1: the padding point in front of a pair group)."""
+    layout, idx = [], []
+    for gr, P_f, _ in groups:
+        ns = len(gr.segs)
+        if ns == 2 and len(idx) % 2:
+            idx.append(-1)
+        layout.append((P_f, len(idx), ns, gr.n))
+        offs = [prog.segments[sg].offset for sg in gr.segs]
+        for k in range(gr.n):
+            idx.extend(o + k for o in offs)
+    return layout, idx, len(idx)
+
+
+# everything that determines the compiled kernel (:func:`recipe`): geometry, stream spec, the number of
+# second-order streams, MFMA layers, bf16x3 (hi + lo operands), points per tile, LDS bytes, kernel name
+# and source (None without a layout)
+KernelRecipe = collections.namedtuple("KernelRecipe", "cfg S spec nso LM lo pt lds name source")
+
+
+def recipe(prog, fop, layout, precision=None):
+    """The :class:`KernelRecipe` of ``prog`` (in ``precision``, default the program's) with the loss
+    groups laid out as ``layout`` (``None``: the geometry alone).  Host only - no GPU call.  Raises
+    ``ValueError`` outside the kernels' envelope."""
+    cfg = hip_config(prog.net, prog.plan, precision or prog.precision)
+    S = cfg["S"]
+    spec = jet_hip.stream_spec(prog.plan)
+    nso = sum(1 for s in range(S) if spec[3 * s] == 2)
+    LM = cfg["n_hidden"] - 1
+    lo = cfg["precision"] == "bf16x3"
+    lds = _lib.load(required=True).tdq_jet_fused_lds(cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"],
+                                                     S, int(lo))
+    if lds < 0 or lds > 160 * 1024:
+        raise ValueError(f"fused step: {lds} bytes of LDS")
+    source = None
+    if layout is not None:
+        gen = gen_loss(layout, fop.n_terms, fop.n_terms + fop.n_scal, S, spec=spec, d_in=cfg["d_in"])
+        source = kernel_source(S, nso, LM, lds, gen, lo=lo)
+    return KernelRecipe(cfg, S, spec, nso, LM, lo, 16 if lo else 32, lds, kernel_name(lo), source)
+
+
+def program_recipe(prog, fop, precision=None):
+    """``(recipe, groups, idx, N)`` of a program's fused step: what :func:`prebuild` compiles and
+    :class:`FusedStepOp` runs."""
+    groups = fused_groups(prog, fop)
+    if isinstance(groups, str):
+        raise ValueError(groups)
+    layout, idx, N = point_layout(prog, groups)
+    return recipe(prog, fop, layout, precision), groups, idx, N
+
+
 def prebuild(prog):
     """Start compiling the fused step of a single-plan program in the background (the L-BFGS
     objective while the Adam phase runs: its hipRTC compile, ~0.35 s, then overlaps the Adam
@@ -311,35 +402,15 @@ def prebuild(prog):
     fop = getattr(prog, "fused_op", None)
     if ineligible(prog, fop) is not None or _mixed(prog):
         return False
-    lib = _lib.load()
-    cfg = hip_config(prog.net, prog.plan, prog.precision)
-    S = cfg["S"]
-    spec = jet_hip.stream_spec(prog.plan)
-    nso = sum(1 for s in range(S) if spec[3 * s] == 2)
-    lo = cfg["precision"] == "bf16x3"
-    lds = lib.tdq_jet_fused_lds(cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"], S, int(lo))
-    gen = gen_loss(_plain_layout(fop.fl), fop.n_terms, fop.n_terms + fop.n_scal, S, spec=spec, d_in=cfg["d_in"])
-    compile_async(kernel_source(S, nso, cfg["n_hidden"] - 1, lds, gen, lo=lo))
+    compile_async(program_recipe(prog, fop)[0].source)
     return True
-
-
-def _plain_layout(fl):
-    """``[(program, start, n_slots, n)]`` of the fused point set of a single-plan program: groups
-    in program order, pair groups on even offsets."""
-    layout, pos = [], 0
-    for gr in fl.groups:
-        ns = len(gr.segs)
-        if ns == 2 and pos % 2:
-            pos += 1
-        layout.append((gr.program, pos, ns, gr.n))
-        pos += ns * gr.n
-    return layout
 
 
 def ineligible(prog, fop):
     """Why the fused step cannot serve this program (``None``: it can)."""
     if not enabled():
         return "TDQ_FUSED_STEP=0"
+    mode = mixed_mode()
     if prog.device.type != "cuda" or fop is None:
         return "needs the fused loss on a GPU"
     try:
@@ -348,163 +419,73 @@ def ineligible(prog, fop):
         return str(e)
     if cfg["precision"] not in ("bf16", "bf16x3") or not jet_hip.is_split_bf16(cfg):
         return f"precision {cfg['precision']}"
-    lo = cfg["precision"] == "bf16x3"
     if cfg["d_out"] != 1:
         return "d_out != 1"
-    lib = _lib.load()
-    if lib.tdq_jet_fused_lds(cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"], cfg["S"], int(lo)) < 0:
+    try:
+        recipe(prog, fop, None)
+    except ValueError:
         return f"network {cfg['widths']} / S={cfg['S']} (width-128 MFMA layers 2-3, S <= 4)"
-    fl = fop.fl
-    for gr in fl.groups:
-        if any(s >= cfg["S"] for (_, s) in gr.program.stream_regs) and not _mixed(prog):
+    if not _mixed(prog):
+        if any(s >= cfg["S"] for gr in fop.fl.groups for (_, s) in gr.program.stream_regs):
             return "a loss group reads streams outside the jet plan"
-    mode = _mixed_mode(prog)
-    if mode is not None and lo:
+        return None
+    if cfg["precision"] == "bf16x3":
         # the bf16x3 objective of a mixed program keeps the point-range launches (its boundary
         # chain runs on the bf16x3 jet_hi kernels beside them)
         return "bf16x3: high-order boundary streams keep the separate launches"
     if mode == "0":
         return "high-order boundary streams (TDQ_FUSED_STEP_MIXED=0)"
-    if mode == "split":
-        sp = _split_groups(prog, fop, cfg["S"])
-        return sp if isinstance(sp, str) else None
-    if mode == "1":
-        # high-order boundary points (jet_hi.hip streams): only the residual group runs fused
-        last = len(prog.segments) - 1
-        gr = fl.groups[-1]
-        if gr.segs != [last] or any(last in g.segs for g in fl.groups[:-1]):
-            return "the last segment is not a group of its own"
-        if any(s >= cfg["S"] for (_, s) in gr.program.stream_regs):
-            return "the residual loss reads streams outside the jet plan"
-        seg = prog.segments[last]
-        if seg.offset + gr.n != prog.X_all.shape[0]:
-            return "the residual segment does not end the point set"
-        if prog.n_hi > seg.offset:
-            return "high-order points inside the residual segment"
-    return None
-
-
-def _mixed(prog):
-    return getattr(prog, "hi_op", None) is not None
-
-
-def _mixed_mode(prog):
-    """Layout of a mixed program (order-3/4 boundary streams from jet_hi.hip), ``TDQ_FUSED_STEP_MIXED``:
-    ``split`` (default) - every loss output on main-plan streams runs in the fused launch (the
-    boundary groups' low-order outputs included), only the high-order outputs' chain (jet_hi
-    forward, their loss blocks, jet_hi adjoint) on a side stream; ``1`` - only the residual group
-    fused, the whole boundary chain on the side stream; ``0`` - the point-range path.  MI355X,
-    AC-baseline 50k: split 0.207 ms/step, residual 0.251, point ranges 0.219-0.226 (AC-SA 0.168;
-    profiles/r5split3_*, r5acb_*).  None: not mixed."""
-    if not _mixed(prog):
-        return None
-    return os.environ.get("TDQ_FUSED_STEP_MIXED", "split")
-
-
-def _split_groups(prog, fop, S):
-    """``[(group, fused program, side program or None)]`` of the split layout, or the reason it
-    does not apply (an output reading main-plan and high-order streams together, or an SA weight
-    read by both halves)."""
-    from .. import fusion
-    out = []
-    for gr in fop.fl.groups:
-        if all(s < S for (_, s) in gr.program.stream_regs):
-            out.append((gr, gr.program, None))
-            continue
-        sp = fusion.split_by_streams(fop.fl, gr, S)
-        if sp is None:
-            return "a loss output reads main-plan and high-order streams together (or both read one SA weight)"
-        out.append((gr, sp[0], sp[1]))
-    return out
+    sp = fused_groups(prog, fop)
+    return sp if isinstance(sp, str) else None
 
 
 class FusedStepOp:
     """The fused training step of a :class:`~tensordiffeq_amd.models.loss.LossProgram` (built by
     :func:`for_program`).
 
-    Single-plan programs: EVERY loss group runs in the one launch - the points re-laid out once
-    into a fused point set (each group's instances contiguous, a periodic group's two segments
-    interleaved pair by pair), so a step is the fused launch + the two-launch step tail.  Precision
-    bf16: 32-point tiles (``jet_fused.h``); bf16x3 (the L-BFGS objective): 16-point tiles with hi +
-    lo operands (``jet_fused3.h``) and fp32 slab rows.  Mixed programs (order-3/4 boundary streams
-    from jet_hi.hip, bf16 only, :func:`_mixed_mode`): split layout - every loss output on main-plan
-    streams in the fused launch, the high-order outputs (their own loss op,
-    :func:`fusion.split_by_streams`) with the jet_hi forward / adjoint on a side stream beside it;
-    residual layout - the residual group fused over its own segment, the whole boundary chain
-    (high-order streams, saved-activation forward, loss blocks, backward) on the side stream."""
+    Single-plan programs (layout ``plain``): EVERY loss group runs in the one launch - the points
+    re-laid out once into a fused point set (:func:`point_layout`), so a step is the fused launch +
+    the two-launch step tail.  Precision bf16: 32-point tiles (``jet_fused.h``); bf16x3 (the L-BFGS
+    objective): 16-point tiles with hi + lo operands (``jet_fused3.h``) and fp32 slab rows.  Mixed
+    programs (order-3/4 boundary streams from jet_hi.hip, bf16 only, :func:`mixed_mode`; layout
+    ``split``): every loss output on main-plan streams in the fused launch, the high-order outputs
+    (their own loss op, :func:`fusion.split_by_streams`) with the jet_hi forward / adjoint on a side
+    stream beside it."""
 
     def __init__(self, prog, fop):
         lib = _lib.load(required=True)
         self.prog, self.fop = prog, fop
-        cfg = self.cfg = hip_config(prog.net, prog.plan, prog.precision)
-        self.lo = cfg["precision"] == "bf16x3"
-        self.pt = 16 if self.lo else 32
-        fl = fop.fl
-        S = cfg["S"]
+        rec, groups, idx, self.N = program_recipe(prog, fop)
+        cfg = self.cfg = rec.cfg
+        self.lo, self.pt, self.lds, self.source = rec.lo, rec.pt, rec.lds, rec.source
         self.nacc = fop.n_terms + fop.n_scal
-        spec = jet_hip.stream_spec(prog.plan)
-        nso = sum(1 for s in range(S) if spec[3 * s] == 2)
-        LM = cfg["n_hidden"] - 1
-        lds = lib.tdq_jet_fused_lds(cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"], S, int(self.lo))
-        if lds < 0 or lds > 160 * 1024:
-            raise ValueError(f"fused step: {lds} bytes of LDS")
-        self.lds = lds
-        N = prog.X_all.shape[0]
         dev = prog.device
         self.mixed = _mixed(prog)
-        self.layout = "plain" if not self.mixed else ("split" if _mixed_mode(prog) == "split" else "residual")
-        self.fop2 = None
-        if self.layout != "residual":
-            # the fused point set: groups in program order, pair groups on even offsets (split
-            # layout: the boundary groups with their main-plan outputs only)
-            groups = [(gr, gr.program, None) for gr in fl.groups] if not self.mixed else _split_groups(prog, fop, S)
-            layout, idx, pos = [], [], 0
-            for gr, P_f, _ in groups:
-                ns = len(gr.segs)
-                if ns == 2 and pos % 2:
-                    idx.append(-1)
-                    pos += 1
-                layout.append((P_f, pos, ns, gr.n))
-                offs = [prog.segments[sg].offset for sg in gr.segs]
-                for k in range(gr.n):
-                    idx.extend(o + k for o in offs)
-                pos += ns * gr.n
-            ix = torch.tensor(idx, dtype=torch.long, device=dev)
-            X_f = prog.X_all[ix.clamp_min(0)].clone()
-            X_f[ix < 0] = 0.0
-            self.X = X_f.contiguous()
-            self.N, self.p_lo, self.srow, self.b_res, self.p_bc, self.seg_lo = pos, 0, 0, 0, 0, 0
-            if self.layout == "split":
-                # the high-order outputs: a loss op of their own (same term / value / lambda / scalar
-                # slots - its pointer table is the main op's), its block rows ahead of the fused rows
-                import copy
-                from ..fusion import Group
-                from .loss_fused import FusedLossOp
-                fl2 = copy.copy(fl)
-                fl2.groups = []
-                for gr, _, P_s in groups:
-                    if P_s is not None:
-                        g2 = Group(list(gr.segs), gr.n)
-                        g2.program = P_s
-                        fl2.groups.append(g2)
-                self.fop2 = FusedLossOp(fl2, prog, fop.lams, fop.scalars, fl.lam_offsets)
-                self.fop2.ptrs = fop.ptrs
-                self.b_res = self.fop2.n_blocks
-        else:
-            self.seg_lo = prog.segments[-1].offset
-            layout = [(fl.groups[-1].program, self.seg_lo, 1, fl.groups[-1].n)]
-            self.X = None                               # the program's X_all
-            self.N, self.p_lo = N, self.seg_lo
-            self.b_res = fop.group_meta[-1][0]          # the residual group's first loss block
-            # boundary points: the saved-activation chain over [0, p_bc) - its backward workgroups
-            # own slab rows [0, srow); points [seg_lo, p_bc) ride along with dJ = 0
-            pts_b = jet_hip.slab_geometry(cfg, N)[0]
-            self.p_bc = min(N, -(-self.seg_lo // 128) * 128) if self.seg_lo > 0 else 0
-            self.srow = -(-self.p_bc // pts_b)
-        self.source = kernel_source(S, nso, LM, lds, gen_loss(layout, fop.n_terms, self.nacc, S, spec=spec,
-                                                              d_in=cfg["d_in"]), lo=self.lo)
-        self.module, self.func = _compile(self.source, kernel_name(self.lo))
-        ntiles = -(-(self.N - self.p_lo) // self.pt)
+        self.layout = "split" if self.mixed else "plain"
+        ix = torch.tensor(idx, dtype=torch.long, device=dev)
+        X_f = prog.X_all[ix.clamp_min(0)].clone()
+        X_f[ix < 0] = 0.0
+        self.X = X_f.contiguous()
+        # prow: the loss-partial rows of the side chain's loss blocks lie ahead of the fused rows
+        self.fop2, self.prow = None, 0
+        if self.mixed:
+            # the high-order outputs: a loss op of their own (same term / value / lambda / scalar
+            # slots - its pointer table is the main op's)
+            import copy
+            from ..fusion import Group
+            from .loss_fused import FusedLossOp
+            fl2 = copy.copy(fop.fl)
+            fl2.groups = []
+            for gr, _, P_s in groups:
+                if P_s is not None:
+                    g2 = Group(list(gr.segs), gr.n)
+                    g2.program = P_s
+                    fl2.groups.append(g2)
+            self.fop2 = FusedLossOp(fl2, prog, fop.lams, fop.scalars, fop.fl.lam_offsets)
+            self.fop2.ptrs = fop.ptrs
+            self.prow = self.fop2.n_blocks
+        self.module, self.func = _compile(self.source, rec.name)
+        ntiles = -(-self.N // self.pt)
         cus = max(1, lib.tdq_device_cus())
         rounds = -(-ntiles // cus)
         if self.fop2 is not None:
@@ -514,26 +495,25 @@ class FusedStepOp:
             # 1.043-1.048 ms/step without it, 1.058-1.060 with it (profiles/r6ao_ac_dist_rounds.txt)
             rounds += int(os.environ.get("TDQ_FS_SPLIT_ROUNDS", "1" if rounds <= 16 else "0"))
         # the fewest workgroups with the same tiles per workgroup (AC-SA 50k, bf16: 1592 tiles,
-        # 228 x 7; bf16x3: 3183 tiles, 245 x 13)
+        # 228 x 7; bf16x3: 3183 tiles, 245 x 13); one gradient-slab row per workgroup
         self.G = -(-ntiles // rounds)
         self.free_cus = cus - self.G   # CUs the persistent workgroups leave to a side chain
-        if self.layout == "residual":   # the fused rows follow the boundary loss blocks' rows in fop.partials
-            self.G = min(self.G, fop.n_blocks - self.b_res)
-        self.rows = self.srow + self.G
-        need = lib.tdq_slab_floats_rows(self.rows, cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"])
-        cap = lib.tdq_jet_bf3_slab_floats(N, cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"])
+        need = lib.tdq_slab_floats_rows(self.G, cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"])
+        cap = lib.tdq_jet_bf3_slab_floats(prog.X_all.shape[0], cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"],
+                                          cfg["n_hidden"])
         if need < 0 or need > cap:
-            raise ValueError(f"fused step: {self.rows} slab rows do not fit the backward's buffer")
-        # loss partials: the boundary loss blocks' rows (mixed) then one row per fused workgroup
-        self.n_lblocks = self.b_res + self.G
+            raise ValueError(f"fused step: {self.G} slab rows do not fit the backward's buffer")
+        # loss partials: the side chain's loss blocks' rows (mixed) then one row per fused workgroup
+        self.n_lblocks = self.prow + self.G
         self.lpart = torch.zeros(max(1, self.n_lblocks * self.nacc), dtype=torch.float32, device=dev)
-        if self.fop2 is not None:   # the side chain's loss blocks write rows [0, b_res) of the same buffer
-            self.fop2.partials = self.lpart[:self.b_res * self.nacc]
-        self._side = torch.cuda.Stream(device=dev) if (self.p_bc > 0 or self.fop2 is not None) else None
+        self._side = None
+        if self.fop2 is not None:   # the side chain's loss blocks write rows [0, prow) of the same buffer
+            self.fop2.partials = self.lpart[:self.prow * self.nacc]
+            self._side = torch.cuda.Stream(device=dev)
 
     def run(self, saved, J, work, flat, pack=True):
         """The step's gradient slabs and loss partials (the fused launch; mixed programs: plus the
-        boundary chain on a side stream, joined before return).  ``saved`` / ``J`` / ``work``: the
+        high-order chain on a side stream, joined before return).  ``saved`` / ``J`` / ``work``: the
         persistent step buffers of ``jet_hip.alloc_forward`` / ``alloc_backward``."""
         lib = _lib.load()
         fop, cfg = self.fop, self.cfg
@@ -542,62 +522,36 @@ class FusedStepOp:
         cur = torch.cuda.current_stream(flat.device)
         side = self._side
         hop = self.prog.hi_op
-        X, _, scratch, _, spec, S = saved
+        _, _, scratch, _, spec, S = saved
         spec_arr = (ctypes.c_int * len(spec))(*spec)
-        Xf = self.X if self.X is not None else X
-        lpart = fop.partials if self.layout == "residual" else self.lpart
-
-        def boundary():
-            if self.fop2 is not None:   # split layout: only the high-order outputs' chain
-                hop.forward(J, flat)
-                self.fop2.run_range(J, 0, self.fop2.n_blocks)
-                hop.backward(self.fop2.dJ, flat)
-                return
-            hop.forward(J, flat)
-            jet_hip.forward_range(saved, J, 0, self.p_bc)
-            if self.b_res > 0:
-                fop.run_range(J, 0, self.b_res)
-            hop.backward(fop.dJ, flat)
-            if self.p_bc > self.seg_lo:
-                fop.dJ[:, self.seg_lo:self.p_bc].zero_()
-            jet_hip.backward_range(saved, fop.dJ, work, 0, self.p_bc)
 
         def fused():
-            rc = lib.tdq_fused_step_launch(self.func, _lib.ptr(Xf), _lib.ptr(scratch), _lib.ptr(work), self.N,
+            rc = lib.tdq_fused_step_launch(self.func, _lib.ptr(self.X), _lib.ptr(scratch), _lib.ptr(work), self.N,
                                            cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"], S,
-                                           spec_arr, self.p_lo, self.srow, self.G, _lib.ptr(fop.ptrs),
-                                           _lib.ptr(lpart), self.b_res, self.nacc, int(self.lo),
-                                           _lib.stream_ptr(flat.device))
+                                           spec_arr, self.G, _lib.ptr(fop.ptrs), _lib.ptr(self.lpart),
+                                           self.prow, self.nacc, int(self.lo), _lib.stream_ptr(flat.device))
             _lib.check(rc, "tdq_fused_step_launch")
 
         if side is None:
             fused()
             return
-        # split layout: which branch is captured first.  With >= 32 CUs left to the side chain
-        # (AC-baseline 50k: 56) the fused launch goes first and no longer starts ~11 us into the step
-        # behind the fork: 0.1638 vs 0.1736 ms/step (profiles/r6aj_ac_baseline_split_order.txt).
-        # With few free CUs (AC-dist 500k: 7) the jet_hi forward launched second waited for the whole
-        # fused launch (964 us) and the chain ran after it (profiles/r6am_*): side chain first
+        # which branch is captured first.  With >= 32 CUs left to the side chain (AC-baseline 50k:
+        # 56) the fused launch goes first and no longer starts ~11 us into the step behind the
+        # fork: 0.1638 vs 0.1736 ms/step (profiles/r6aj_ac_baseline_split_order.txt).  With few free
+        # CUs (AC-dist 500k: 7) the jet_hi forward launched second waited for the whole fused launch
+        # (964 us) and the chain ran after it (profiles/r6am_*): side chain first
         order = os.environ.get("TDQ_FS_SPLIT_ORDER", "fused_first" if self.free_cus >= 32 else "side_first")
-        if self.fop2 is not None and order == "side_first":
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                boundary()
-            fused()
-            cur.wait_stream(side)
-            return
-        # the fused launch is the graph's first node and the boundary branch forks from before it:
-        # MI355X, AC-SA (side chain layout): 0.1697 vs 0.1813 ms/step with the branch captured
-        # first (profiles/r5ord_*: the fused kernel then started ~6 us later and the join waited
-        # ~10 us on the other queue)
         ev = torch.cuda.Event()
         ev.record(cur)
-        fused()
+        if order != "side_first":
+            fused()
         side.wait_event(ev)
-        with torch.cuda.stream(side):
-            boundary()
+        with torch.cuda.stream(side):   # the high-order outputs' chain
+            hop.forward(J, flat)
+            self.fop2.run_range(J, 0, self.fop2.n_blocks)
+            hop.backward(self.fop2.dJ, flat)
+        if order == "side_first":
+            fused()
         cur.wait_stream(side)
 
     def set_timing_buffer(self, buf):
@@ -608,8 +562,7 @@ class FusedStepOp:
     def tail_kw(self):
         """Keyword arguments of ``jet_hip.step_tail`` / ``dp_tail_a`` for this step's rows (the slab
         precision follows the program's: bf16 rows for bf16, fp32 rows for bf16x3)."""
-        return {"rows": self.rows, "lpart": self.fop.partials if self.layout == "residual" else self.lpart,
-                "n_lblocks": self.n_lblocks}
+        return {"rows": self.G, "lpart": self.lpart, "n_lblocks": self.n_lblocks}
 
 
 def for_program(prog):

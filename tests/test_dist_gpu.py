@@ -121,7 +121,7 @@ def _forced_worker(q, precision, dp_graph, n_f=N_F, split="auto", iters=8, unrol
     m.fit(tf_iter=iters)
     eng = m._get_engine(None, 1)
     res = {"hist": [h["Total Loss"] for h in m.losses], "flat": m.u_model.flat.detach().cpu().numpy().copy(),
-           "one_graph": eng.graph_b is None, "ranges": getattr(eng, "_ranges", None),
+           "one_graph": eng.graph_b is None, "ranges": eng.points.ranges(),
            "k_graph": getattr(eng, "graph_k", None) is not None}
     m.fit(newton_iter=3)
     res["lbfgs_loss"] = float(m.min_loss["l-bfgs"])

@@ -1,4 +1,4 @@
-"""One-launch residual training step (ops/fused_step.py, csrc/jet_fused.h MODE 2).
+"""One-launch training step (ops/fused_step.py, csrc/jet_fused.h: the fused step).
 
 CPU: the generated kernels (headers + the program's loss as ``GenLoss``; the bf16 step and the
 bf16x3 objective) compile with hipRTC for gfx950 for several traced programs, and eligibility is
@@ -44,43 +44,102 @@ def _compile_ok(src):
     lib.tdq_rtc_free(code)
 
 
+def _prog_op(m):
+    from tensordiffeq_amd.ops.loss_fused import FusedLossOp
+    prog = m.program()
+    fl = fusion.build(prog, m.lambdas)
+    return prog, FusedLossOp(fl, prog, m.lambdas, fusion.scalar_values(fl, m.lambdas, None), fl.lam_offsets)
+
+
 @pytest.mark.parametrize("problem,layers", [("ac", [2, 128, 128, 128, 128, 1]), ("ac_g", [2, 128, 128, 128, 1]),
                                             ("burgers", [2, 128, 128, 128, 128, 1]), ("ac", [2, 128, 128, 1])])
 def test_fused_step_source_compiles(problem, layers):
-    from tensordiffeq_amd.ops import _lib, fused_step, jet_hip
-    from tensordiffeq_amd.ops.jet_mlp import hip_config
-    from tensordiffeq_amd.ops.loss_fused import FusedLossOp
+    from tensordiffeq_amd.ops import _lib, fused_step
     if not _lib.available():
         pytest.skip("native library not built")
-    m = _deep(problem, layers)
-    prog = m.program()
-    fl = fusion.build(prog, m.lambdas)
-    op = FusedLossOp(fl, prog, m.lambdas, fusion.scalar_values(fl, m.lambdas, None), fl.lam_offsets)
+    prog, op = _prog_op(_deep(problem, layers))
     # the residual group is the last group, alone on the last segment
     last = len(prog.segments) - 1
-    assert fl.groups[-1].segs == [last]
-    cfg = hip_config(prog.net, prog.plan, "bf16")
-    lib = _lib.load()
-    lds = lib.tdq_jet_fused_lds(cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"], cfg["S"], 0)
-    if lds < 0:   # a 1-MFMA-layer net ([2, 128, 128, 1]): MODE 2 needs two
-        assert cfg["n_hidden"] - 1 < 2
+    assert op.fl.groups[-1].segs == [last]
+    layout, _, _ = fused_step.point_layout(prog, fused_step.fused_groups(prog, op))
+    if len(layers) - 3 < 2:   # a 1-MFMA-layer net ([2, 128, 128, 1]): the fused step needs two
+        with pytest.raises(ValueError):
+            fused_step.recipe(prog, op, layout, "bf16")
         return
-    spec = jet_hip.stream_spec(prog.plan)
-    nso = sum(1 for s in range(cfg["S"]) if spec[3 * s] == 2)
-    layout, pos = [], 0
-    for gr in fl.groups:
-        ns = len(gr.segs)
-        pos += pos % 2 if ns == 2 else 0
-        layout.append((gr.program, pos, ns, gr.n))
-        pos += ns * gr.n
-    gen = fused_step.gen_loss(layout, op.n_terms, op.n_terms + op.n_scal, cfg["S"], spec=spec, d_in=cfg["d_in"])
+    rec = fused_step.recipe(prog, op, layout, "bf16")
+    gen = rec.source[len(fused_step.header_source()):]
     assert "JV(" in gen and "UB(" in gen
     if problem == "ac":   # the periodic pair group reads its partner point
         assert "t + 1" in gen
-    _compile_ok(fused_step.kernel_source(cfg["S"], nso, cfg["n_hidden"] - 1, lds, gen))
-    lds3 = lib.tdq_jet_fused_lds(cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"], cfg["S"], 1)
-    assert 0 < lds3 <= 160 * 1024, lds3
-    _compile_ok(fused_step.kernel_source(cfg["S"], nso, cfg["n_hidden"] - 1, lds3, gen, lo=True))
+    _compile_ok(rec.source)
+    rec3 = fused_step.recipe(prog, op, layout, "bf16x3")
+    assert 0 < rec3.lds <= 160 * 1024, rec3.lds
+    _compile_ok(rec3.source)
+
+
+def test_point_layout():
+    """Pair groups start on even offsets with their two segments' points alternating; ``idx`` is -1
+    exactly at the padding points; ``N`` counts every slot and pad."""
+    from types import SimpleNamespace as NS
+    from tensordiffeq_amd.ops import fused_step
+
+    def check(prog, groups):
+        layout, idx, N = fused_step.point_layout(prog, groups)
+        assert N == len(idx) and [la[0] for la in layout] == [g[1] for g in groups]
+        covered = set()
+        for (gr, _, _), (_, start, ns, n) in zip(groups, layout):
+            assert ns == len(gr.segs) and n == gr.n
+            offs = [prog.segments[sg].offset for sg in gr.segs]
+            if ns == 2:
+                assert start % 2 == 0
+            for k in range(n):
+                assert idx[start + ns * k:start + ns * (k + 1)] == [o + k for o in offs]
+            covered.update(range(start, start + ns * n))
+        pads = [i for i in range(N) if i not in covered]
+        assert [i for i, v in enumerate(idx) if v == -1] == pads
+        assert N == sum(ns * n for (_, _, ns, n) in layout) + len(pads)
+        return layout, pads
+
+    prog, op = _prog_op(_deep("ac", [2, 128, 128, 128, 128, 1]))
+    layout, _ = check(prog, fused_step.fused_groups(prog, op))
+    assert any(ns == 2 for (_, _, ns, _) in layout)
+    prog, op = _prog_op(_deep("burgers", [2, 128, 128, 128, 128, 1]))
+    layout, pads = check(prog, fused_step.fused_groups(prog, op))
+    assert all(ns == 1 for (_, _, ns, _) in layout) and not pads
+    # a pair group behind an odd number of points: one pad in front of it
+    prog = NS(segments=[NS(offset=0), NS(offset=3), NS(offset=5), NS(offset=7)])
+    _, pads = check(prog, [(NS(segs=[0], n=3), "a", None), (NS(segs=[1, 2], n=2), "b", None),
+                           (NS(segs=[3], n=1), "c", None)])
+    assert pads == [3]
+
+
+@pytest.mark.parametrize("problem", ["ac", "burgers"])
+@pytest.mark.parametrize("precision", ["bf16", "bf16x3"])
+def test_prebuild_source_is_the_ops_source(problem, precision):
+    """What ``prebuild`` compiles in the background (``program_recipe``) is, for a plain program,
+    the source of every group laid out whole - the kernel ``FusedStepOp`` then asks for."""
+    from tensordiffeq_amd.ops import _lib, fused_step
+    if not _lib.available():
+        pytest.skip("native library not built")
+    prog, op = _prog_op(_deep(problem, [2, 128, 128, 128, 128, 1]))
+    rec, groups, idx, N = fused_step.program_recipe(prog, op, precision)
+    whole = [(gr, gr.program, None) for gr in op.fl.groups]
+    assert groups == whole
+    ref = fused_step.recipe(prog, op, fused_step.point_layout(prog, whole)[0], precision)
+    assert rec.source == ref.source and rec.name == ref.name == fused_step.kernel_name(precision == "bf16x3")
+    assert rec.lo == (precision == "bf16x3") and rec.pt == (16 if rec.lo else 32)
+
+
+def test_mixed_mode_values(monkeypatch):
+    from tensordiffeq_amd.ops import fused_step
+    monkeypatch.delenv("TDQ_FUSED_STEP_MIXED", raising=False)
+    assert fused_step.mixed_mode() == "split"
+    for v in ("split", "0"):
+        monkeypatch.setenv("TDQ_FUSED_STEP_MIXED", v)
+        assert fused_step.mixed_mode() == v
+    monkeypatch.setenv("TDQ_FUSED_STEP_MIXED", "1")
+    with pytest.raises(ValueError, match="'split' and '0'"):
+        fused_step.mixed_mode()
 
 
 def test_fused_step_not_on_cpu():
@@ -102,7 +161,6 @@ def _acsa(n_f, seed=0, problem="ac-sa", precision="bf16"):
 @pytest.mark.parametrize("problem,n_f,mixed,precision", [("ac-sa", 50000, "split", "bf16"),
                                                          ("ac-sa", 3001, "split", "bf16"),
                                                          ("ac-baseline", 20000, "split", "bf16"),
-                                                         ("ac-baseline", 20000, "1", "bf16"),
                                                          ("ac-sa", 50000, "split", "bf16x3"),
                                                          ("ac-sa", 3001, "split", "bf16x3")])
 def test_fused_step_matches_separate_launches(problem, n_f, mixed, precision, monkeypatch):
@@ -110,7 +168,7 @@ def test_fused_step_matches_separate_launches(problem, n_f, mixed, precision, mo
     step vs the separate launches (saved-activation kernels + specialized loss kernel).  AC-SA runs
     every group in the fused launch (IC with SA weights, the periodic pairs, the residual);
     AC-baseline (order-4 periodic streams): split layout - every main-plan output fused, the
-    u_xxx / u_xxxx outputs on the jet_hi side chain; layout "1" - the residual only."""
+    u_xxx / u_xxxx outputs on the jet_hi side chain."""
     monkeypatch.setenv("TDQ_FUSED_STEP_MIXED", mixed)
     from tensordiffeq_amd.fit import LossGradEngine
     from tensordiffeq_amd.ops import fused_step
@@ -125,7 +183,7 @@ def test_fused_step_matches_separate_launches(problem, n_f, mixed, precision, mo
             assert fs is not None, prog.fused_step_reason
             assert fs.mixed == (problem == "ac-baseline")
             if fs.mixed:
-                assert fs.layout == ("split" if mixed == "split" else "residual")
+                assert fs.layout == "split"
             assert fs.lo == (precision == "bf16x3")
         else:
             assert fs is None

@@ -629,14 +629,14 @@ def test_point_ranges_match_single_launch(prec, cuts, monkeypatch):
         m = _ac_sa_model(prec, n_f=20000)
         m.fit(tf_iter=40)
         eng = m._get_engine(None, 1)
-        assert (eng._ranges is None) == (split == "0")
+        assert (eng.points.ranges() is None) == (split == "0")
         hist = [h["Total Loss"] for h in m.losses]
         flat = m.u_model.flat.detach().clone()
         lam = m.lambdas[0].detach().clone()
         from tensordiffeq_amd.fit import LossGradEngine
         le = LossGradEngine(m, m.program(precision=prec), m.lambdas)
         f0, g0 = le(m.u_model.flat.detach().clone())
-        assert (le._ranges is None) == (split == "0")
+        assert (le.points.ranges() is None) == (split == "0")
         m.fit(newton_iter=30)
         res.append((hist, flat, lam, float(f0), g0.clone(), m.u_model.flat.detach().clone()))
     a, b = res

@@ -14,32 +14,16 @@ sys.path.insert(0, ROOT)
 
 
 def sources():
+    import torch
+    import bench
     from tensordiffeq_amd import fusion
-    from tensordiffeq_amd.ops import _lib, fused_step, jet_hip
-    from tensordiffeq_amd.ops.jet_mlp import hip_config
+    from tensordiffeq_amd.ops import fused_step
     from tensordiffeq_amd.ops.loss_fused import FusedLossOp
-    from tests.test_fused_step import _deep
-    m = _deep("ac", [2, 128, 128, 128, 128, 1])
+    m = bench.build_problem(400, 1, "jet", torch.device("cpu"), False)
     prog = m.program()
     fl = fusion.build(prog, m.lambdas)
     op = FusedLossOp(fl, prog, m.lambdas, fusion.scalar_values(fl, m.lambdas, None), fl.lam_offsets)
-    cfg = hip_config(prog.net, prog.plan, "bf16")
-    lib = _lib.load()
-    spec = jet_hip.stream_spec(prog.plan)
-    S = cfg["S"]
-    nso = sum(1 for s in range(S) if spec[3 * s] == 2)
-    layout, pos = [], 0
-    for gr in fl.groups:
-        ns = len(gr.segs)
-        pos += pos % 2 if ns == 2 else 0
-        layout.append((gr.program, pos, ns, gr.n))
-        pos += ns * gr.n
-    gen = fused_step.gen_loss(layout, op.n_terms, op.n_terms + op.n_scal, S, spec=spec, d_in=cfg["d_in"])
-    out = {}
-    for lo in (0, 1):
-        lds = lib.tdq_jet_fused_lds(cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"], S, lo)
-        out["bf16x3" if lo else "bf16"] = fused_step.kernel_source(S, nso, cfg["n_hidden"] - 1, lds, gen, lo=bool(lo))
-    return out
+    return {prec: fused_step.program_recipe(prog, op, prec)[0].source for prec in ("bf16", "bf16x3")}
 
 
 def main():

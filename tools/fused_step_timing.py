@@ -1,4 +1,4 @@
-"""Per-phase cycles of the fused training step (ops/fused_step.py, csrc/jet_fused.h MODE 2) from
+"""Per-phase cycles of the fused training step (ops/fused_step.py, csrc/jet_fused.h: the fused step) from
 in-kernel s_memtime stamps of the first tile of every workgroup.
 
 The run-time compiled kernel is built with ``-DTDQ_PHASE_TIMING`` (``TDQ_FUSED_STEP_TIMING=1``),
@@ -58,7 +58,7 @@ def main():
         print(f"  {NAMES.get(k, k):28s} {np.median(d):9.0f} {np.percentile(d, 90):9.0f}")
         prev = k
     tot = t[:, 62] - t[:, 0]
-    ntl = -(-(fs.N - fs.p_lo) // fs.pt)
+    ntl = -(-fs.N // fs.pt)
     print(f"  {'tile loop total':28s} {np.median(tot):9.0f} {np.percentile(tot, 90):9.0f}"
           f"   ({ntl} tiles over {fs.G} workgroups)")
 
