@@ -41,6 +41,14 @@ def _flags(defines=()):
              "-Wno-unused-result", "-I", HERE] + [f"-D{m}" for m in defines])
 
 
+# Per-file flags.  loss_fused.hip: the bytecode interpreter promises the bits of the hipRTC-specialised
+# kernels (ops/loss_jit.py), which are compiled with statement-level FMA contraction.  hipcc's default
+# (-ffp-contract=fast) also lets the backend fuse inside the expansions of logf / sinf / cosf / expf /
+# tanhf / powf (logf: the final v_mul + v_add of the ln(2) scaling becomes one v_fmac), a last-bit
+# difference between the two (tests/test_loss_jit.py, program "log").
+FILE_FLAGS = {"loss_fused.hip": ["-ffp-contract=on"]}
+
+
 def source_files():
     return sorted(glob.glob(os.path.join(HERE, "*.hip")) + glob.glob(os.path.join(HERE, "*.h")))
 
@@ -66,7 +74,7 @@ def _stamp(src, cmd):
 
 def _compile(src, force, build_dir=None, defines=()):
     obj = os.path.join(build_dir or BUILD, os.path.basename(src).replace(".hip", ".o"))
-    cmd = [hipcc()] + _flags(defines) + ["-c", src, "-o", obj]
+    cmd = [hipcc()] + _flags(defines) + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
     stamp = _stamp(src, cmd)
     sfile = obj + ".stamp"
     if not force and os.path.exists(obj) and os.path.exists(sfile):

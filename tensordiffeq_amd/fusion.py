@@ -163,7 +163,8 @@ class Sym:
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
+        # a keyword left at None is the call's default (rounding_mode=None, out=None)
+        kwargs = {k: v for k, v in (kwargs or {}).items() if v is not None}
         name = getattr(func, "__name__", str(func)).lstrip("_").rstrip("_")
         syms = [a for a in args if isinstance(a, Sym)]
         if name in ("cat", "stack", "hstack", "concat"):
@@ -173,6 +174,17 @@ class Sym:
         if not syms:
             raise TraceError(f"unsupported torch function {name}")
         s = syms[0]
+        if name in ("reshape", "view", "squeeze", "unsqueeze", "contiguous", "clone", "float"):
+            return s
+        # torch.add / torch.sub(a, b, alpha=c) = a +- c * b; every other keyword of an arithmetic
+        # call (rounding_mode, out, dtype, ...) changes what it computes in a way the tracer does
+        # not express
+        alpha = kwargs.pop("alpha", None) if name in ("add", "sub") and len(args) == 2 else None
+        if kwargs:
+            raise TraceError(f"torch.{name}() with keyword argument(s) {sorted(kwargs)} in a traced expression")
+        if alpha is not None:
+            scaled = s._c(args[1]) * s._c(alpha)
+            return s._c(args[0]) + scaled if name == "add" else s._c(args[0]) - scaled
         if name in ("add", "radd"):
             return s._c(args[0]) + s._c(args[1]) if len(args) > 1 else s
         if name in ("sub", "rsub"):
@@ -193,8 +205,6 @@ class Sym:
             return -s
         if name in UNARY:
             return s._un(name)
-        if name in ("reshape", "view", "squeeze", "unsqueeze", "contiguous", "clone", "float"):
-            return s
         raise TraceError(f"unsupported torch function {name}")
 
 
@@ -484,6 +494,16 @@ def _build(prog, lambdas):
         gr.program = compile_graph(g, gr.outputs, stream_index, fl.n_streams, val_ids, lam_ids, scal_id)
         gr.graph = g
         fl.groups.append(gr)
+    # every executor ASSIGNS the per-point SA-weight gradient (dlam[a][i] = g): a weight array read by
+    # two groups (a periodic BC over several variables, a Neumann BC over several faces) would keep
+    # one group's adjoint only, where the loss sums them (split_by_streams refuses the same overlap)
+    owner = {}
+    for gi, gr in enumerate(fl.groups):
+        for a in _lam_ids(gr.program):
+            if a in owner:
+                raise TraceError(f"per-point weights of lambda {fl.lam_slots[a]} are read by loss groups "
+                                 f"{owner[a]} and {gi}")
+            owner[a] = gi
     fl.compile_ctx = (stream_index, fl.n_streams, val_ids, lam_ids, scal_id)
     return fl
 

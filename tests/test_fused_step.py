@@ -77,6 +77,29 @@ def test_fused_step_source_compiles(problem, layers):
     _compile_ok(rec3.source)
 
 
+@pytest.mark.parametrize("pack", ["A", "B", "C", "D"])
+def test_fused_step_source_compiles_opcode_zoo(pack):
+    """The packed opcode programs of tests/test_loss_ops_oracle.py (every opcode, COORD loads, the
+    SCAL adjoint, a VAL-first prefetch, groups without a partner) as ``GenLoss``: the bf16 and the
+    bf16x3 kernel compile for gfx950 on the network the GPU leg uses."""
+    from tensordiffeq_amd.ops import _lib, fused_step
+    from tests.test_loss_ops_oracle import LAYERS4, zoo_model
+    if not _lib.available():
+        pytest.skip("native library not built")
+    prog, op = _prog_op(zoo_model(pack, "cpu", "jet", n_f=400, layers=LAYERS4))
+    layout, _, _ = fused_step.point_layout(prog, fused_step.fused_groups(prog, op))
+    for precision in ("bf16", "bf16x3"):
+        rec = fused_step.recipe(prog, op, layout, precision)
+        gen = rec.source[len(fused_step.header_source()):]
+        if pack == "A":
+            assert "xs[(t + 0) * TDQ_MAXD + 0]" in gen             # COORD from the tile
+        if pack == "C":
+            assert f"acc[{op.n_terms}] +=" in gen                  # SCAL adjoint
+        if pack == "D":
+            assert "t + 1" not in gen and "return ptr.val[" in gen  # no pair group, VAL prefetched
+        _compile_ok(rec.source)
+
+
 def test_point_layout():
     """Pair groups start on even offsets with their two segments' points alternating; ``idx`` is -1
     exactly at the padding points; ``N`` counts every slot and pad."""

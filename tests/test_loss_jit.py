@@ -14,6 +14,7 @@ import torch
 
 import tensordiffeq_amd as tdq
 from tensordiffeq_amd import fusion
+from tests.test_loss_ops_oracle import ZOO_NEW, zoo_model
 from tests.test_solver import allen_cahn, burgers
 
 
@@ -45,6 +46,8 @@ def _neumann_sin(device, backend, width=8):
 def _model(problem, device, backend, width=8, n_f=400):
     if problem == "neumann":
         return _neumann_sin(device, backend, width)
+    if problem in ZOO_NEW:
+        return zoo_model(problem, device, backend, width=width, n_f=n_f)
     torch.manual_seed(0)
     m = tdq.CollocationSolverND(verbose=False)
     if problem == "burgers":
@@ -60,7 +63,9 @@ def _model(problem, device, backend, width=8, n_f=400):
     return m
 
 
-PROBLEMS = ["ac", "burgers", "ac_g", "neumann"]
+# + one program per opcode family (tests/test_loss_ops_oracle.py): TANH, LOG, COS, NEG, SQUARE, POWI /
+# POWF edge exponents, DIV by a stream, SCAL - the library calls of both translation units
+PROBLEMS = ["ac", "burgers", "ac_g", "neumann"] + ZOO_NEW
 
 
 @pytest.mark.parametrize("problem", PROBLEMS)
