@@ -172,35 +172,70 @@ __device__ __forceinline__ f32x4 fz_bf4(bf16x4 v) {
                __uint_as_float(u[1] & 0xffff0000u)};
 }
 
-// acc[oo][s] = sum_kb A(o0 + oo, kb) B(kb, s) for the 16 points of column tile q: A from a weight
-// image in global memory (hi only, one k-block ahead), B from the LDS image `im` (S stream images of
-// FZ_PT rows; the SIMD's other wave covers the LDS latency).
-template <int WT, int S, int OPW>
-__device__ __forceinline__ void fz_gemm(f32x4 (&acc)[OPW][S], const bf16x8* __restrict__ wimg, int layer, int o0,
-                                        const __bf16* im, int q, const FzLane& L, int l) {
-  constexpr int KB = WT / 2, RS = bf3_img_rs(WT), SIMG = FZ_PT * RS, NSTEP = WT * KB;
+// A fragments (hi only) of a GEMM: the wave's OPW output tiles of a weight image in global memory
+// (L2 resident), one 16-byte buffer load per lane, k-block and tile; FZ_WAHEAD k-blocks in flight
+// ahead of the MFMAs.  fz_body issues the first FZ_WAHEAD k-blocks (fz_pre_w) BEFORE the workgroup
+// barrier that precedes the GEMM, after the epilogue's arithmetic and LDS stores: the weights
+// depend on nothing the barrier protects, so their round trip runs under the barrier wait, and
+// the fragments are live only while the epilogue's temporaries are dead.  fz_gemm issues k-block
+// kb + FZ_WAHEAD beside the MFMAs of k-block kb.  Measured (AC-SA 50k, ms per step;
+// profiles/r8b_weight_prefetch_variants.jsonl, phase stamps profiles/r8b_phases_bf16_*.txt):
+//   one k-block ahead, first issued after the barrier (before this change)   0.1394 / 0.1412
+//   two ahead, first two before the barrier (in use)                         0.1366 / 0.1360
+//   one ahead, first before the barrier                                      0.1373 / 0.1408
+//   two ahead, first two after the barrier                                   0.1407 / 0.1410
+//   all four before the barrier                                              0.1443 / 0.1439
+//   all four at the GEMM's start, after the barrier                          0.1432 / 0.1428
+// A GEMM's fragments are 64 KB per workgroup (8 waves x 8 loads x 1 KB): ~1000 cycles of the CU's
+// 64 B/clk vector-memory path, as long as its MFMAs.  All of them in one burst hold the waves at
+// the issue (the phase in front of the barrier grew by ~650 cycles) and, in the forward GEMMs, the
+// compiler waits for the last before the first MFMA.
+template <int WT, int OPW>
+struct FzW {
+  bf16x8 a[WT / 2][OPW];
+};
+constexpr int FZ_WAHEAD = 2;
+// k-block kb of the fragments (no-op past the last k-block)
+template <int WT, int OPW>
+__device__ __forceinline__ void fz_load_w(FzW<WT, OPW>& w, const bf16x8* __restrict__ wimg, int layer, int o0, int l,
+                                          int kb) {
+  constexpr int KB = WT / 2, NSTEP = WT * KB;
+  if (kb >= KB) return;
   const Tl Wi = tl_make(wimg + (size_t)(layer - 1) * NSTEP * 128, l);
-  bf16x8 a[2][OPW], alo[2][OPW];
 #pragma unroll
-  for (int oo = 0; oo < OPW; ++oo) img_frag<false>(Wi, (o0 + oo) * KB, a[0][oo], alo[0][oo]);
+  for (int oo = 0; oo < OPW; ++oo) {
+    bf16x8 unused;
+    img_frag<false>(Wi, (o0 + oo) * KB + kb, w.a[kb][oo], unused);
+  }
+}
+// the first FZ_WAHEAD k-blocks: in front of the barrier that precedes fz_gemm
+template <int WT, int OPW>
+__device__ __forceinline__ void fz_pre_w(FzW<WT, OPW>& w, const bf16x8* __restrict__ wimg, int layer, int o0, int l) {
+#pragma unroll
+  for (int kb = 0; kb < FZ_WAHEAD; ++kb) fz_load_w<WT, OPW>(w, wimg, layer, o0, l, kb);
+}
+
+// acc[oo][s] = sum_kb A(o0 + oo, kb) B(kb, s) for the 16 points of column tile q: A from the weight
+// fragments (the first FZ_WAHEAD k-blocks loaded by fz_pre_w, the others here), B from the LDS image
+// `im` (S stream images of FZ_PT rows; the SIMD's other wave covers the LDS latency).
+template <int WT, int S, int OPW>
+__device__ __forceinline__ void fz_gemm(f32x4 (&acc)[OPW][S], FzW<WT, OPW>& w, const bf16x8* __restrict__ wimg, int layer,
+                                        int o0, int l, const __bf16* im, int q, const FzLane& L) {
+  constexpr int KB = WT / 2, RS = bf3_img_rs(WT), SIMG = FZ_PT * RS;
 #pragma unroll
   for (int oo = 0; oo < OPW; ++oo)
 #pragma unroll
     for (int s = 0; s < S; ++s) acc[oo][s] = zero4();
 #pragma unroll
   for (int kb = 0; kb < KB; ++kb) {
-    if (kb + 1 < KB) {
-#pragma unroll
-      for (int oo = 0; oo < OPW; ++oo)
-        img_frag<false>(Wi, (o0 + oo) * KB + kb + 1, a[(kb + 1) & 1][oo], alo[(kb + 1) & 1][oo]);
-    }
+    fz_load_w<WT, OPW>(w, wimg, layer, o0, l, kb + FZ_WAHEAD);
     bf16x8 b[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) b[s] = fz_bfrag<RS>(im + s * SIMG, L, q, kb);
 #pragma unroll
     for (int oo = 0; oo < OPW; ++oo)
 #pragma unroll
-      for (int s = 0; s < S; ++s) acc[oo][s] = mfma_bf(a[kb & 1][oo], b[s], acc[oo][s]);
+      for (int s = 0; s < S; ++s) acc[oo][s] = mfma_bf(w.a[kb][oo], b[s], acc[oo][s]);
     // (a scheduling barrier per k-block: without it the step took 0.152 vs 0.146 ms, gpurun_out r6n)
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -383,6 +418,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
 
 
   int t = t0;
+  FzW<WT, OPW> wf;  // the next GEMM's weight fragments (fz_pre_w in front of the barrier, the rest in fz_gemm)
   TDQ_TS(0);
   while (t < t1) {
     const int pb = t * FZ_PT;
@@ -402,6 +438,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
 #pragma unroll
       for (int s = 0; s < S; ++s) fz_put<RS>(slot(0) + s * SIMG, L, q, o0 + oo, cvt_hi4(h[s]));
     }
+    fz_pre_w<WT, OPW>(wf, Wimg, 1, o0, l);
     __syncthreads();
     FZ_TS(2);
 
@@ -410,7 +447,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
     for (int ly = 1; ly <= LM; ++ly) {
       const float* bi = aux + A_BH + (ly - 1) * W;
       f32x4 acc[OPW][S];
-      fz_gemm<WT, S, OPW>(acc, Wimg, ly, o0, slot(ly - 1), q, L, l);
+      fz_gemm<WT, S, OPW>(acc, wf, Wimg, ly, o0, l, slot(ly - 1), q, L);
       FZ_TS(1 + 2 * ly);
       f32x4 hq[OPW][S];  // top layer: the streams for the output dots
 #pragma unroll
@@ -446,6 +483,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
           if (g == 0) outp[(wo * S + s) * FZ_PT + row] = r;
         }
       }
+      if (ly < LM) fz_pre_w<WT, OPW>(wf, Wimg, ly + 1, o0, l);
       __syncthreads();
       FZ_TS(2 + 2 * ly);
     }
@@ -493,6 +531,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
 #pragma unroll
       for (int s = 0; s < S; ++s) fz_put<RS>(im + s * SIMG, L, q, to, cvt_hi4(zb[s]));
     }
+    fz_pre_w<WT, OPW>(wf, Kimg, LM, o0, l);
     __syncthreads();
     // ---- hidden layers LM..1: dK_l, hb_{l-1} = K_l zb_l, adjoint of tanh layer l-1 --------
 #pragma unroll
@@ -501,7 +540,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
       __bf16* H = slot(ly - 1);
       const int tb = 10 + 5 * (LM - ly);
       f32x4 acc[OPW][S];
-      fz_gemm<WT, S, OPW>(acc, Kimg, ly, o0, Z, q, L, l);
+      fz_gemm<WT, S, OPW>(acc, wf, Kimg, ly, o0, l, Z, q, L);
       FZ_TS(tb);
       // the tanh-jet adjoint (VALU) and dK_ly (MFMA: every wave reads all of H and Z) in one
       // scheduling region; zb_{ly-1} goes in place of h_{ly-1} after the barrier
@@ -585,7 +624,10 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
           for (int s = 1; s < S; ++s) fz_put<RS>(slot(0) + s * SIMG, L, q, o0 + oo, cvt_hi4(h[s]));
         }
       }
-      if (ly >= 2) __syncthreads();
+      if (ly >= 2) {
+        fz_pre_w<WT, OPW>(wf, Kimg, ly - 1, o0, l);
+        __syncthreads();
+      }
       FZ_TS(tb + 4);
     }
     ++t;

@@ -44,10 +44,22 @@ __host__ __device__ inline int fz3_lds_bytes(const NetDims& d, int WT, int S, in
   return fz_nslot(LM) * fz3_slot_bytes(WT, S) + fz3_fl_floats(d, WT, S, LM) * 4;
 }
 
-// A fragments (hi + lo, every k-block) of one GEMM's weight-image rows, all issued at the GEMM's
-// start (one L2 latency per GEMM).  Issuing them one phase ahead (right after the previous GEMM's
-// MFMAs, so the latency hides behind the epilogue / loss) measured SLOWER: 430 vs 324 us per
-// objective evaluation - the 32 extra live VGPRs spilled (28 vs 12, gpurun_out r6e)
+// A fragments (hi + lo, every k-block) of one GEMM's weight-image rows.  In use: all issued at the
+// GEMM's start, behind the workgroup barrier that precedes it (one L2 latency per GEMM).
+// Placements that were measured and are not in use:
+//   * one phase ahead (right after the previous GEMM's MFMAs, so the latency hides behind the
+//     epilogue / loss): SLOWER, 430 vs 324 us per objective evaluation - the 32 extra VGPRs held
+//     across the tanh-jet epilogue spilled (28 vs 12);
+//   * all of them directly BEFORE that barrier, after the epilogue's arithmetic and LDS stores (no
+//     more spills: 15 either way): SLOWER, L-BFGS 0.3045-0.3052 vs 0.3009-0.3017 ms per iteration
+//     (profiles/r8b_lbfgs_all_before_barrier.jsonl) - the burst of eight 1 KB loads per wave holds
+//     the waves in front of the barrier (that phase +650 cycles, every GEMM +100,
+//     profiles/r8b_phases_bf16x3_*.txt);
+//   * only the first k-block (two loads) before the barrier, the rest at the GEMM's start:
+//     0.2989-0.2995 vs 0.3010-0.3020 ms per iteration, every run ahead of every parent run but the
+//     median gain (0.0023 ms, 0.75 %) under three times the parent's spread in that call
+//     (0.0010 ms): not taken (profiles/r8d_lbfgs_first_kblock_ab.jsonl,
+//     profiles/r8c_lbfgs_prefetch_variants.jsonl).  The bf16 step's fz_pre_w is this move.
 template <int WT>
 struct Fz3W {
   bf16x8 h[WT / 2], l[WT / 2];
