@@ -623,7 +623,6 @@ int tdq_fused_step_launch(void* func, const float* X, float* scratch, float* wor
   P.Pst = slab_stride(param_count(d));
   P.ntiles = (N + PT - 1) / PT;
   P.d = d;
-  P.sp = sp;
   P.lptrs = reinterpret_cast<const FzLossPtrs*>(lptrs);
   P.lpart = lpart;
   P.prow = prow;

@@ -54,18 +54,32 @@ __host__ __device__ constexpr int fz_nslot(int LM) { return LM < 2 ? 2 : LM; }
 __host__ __device__ constexpr int fz_img_elems(int WT, int S, int LM) {
   return (S + 1) * fz_nslot(LM) * FZ_PT * bf3_img_rs(WT);
 }
-// float area after the images: aux copy | xs | ubs | per-column-tile partials (biases of layers
-// 0..LM, K0, Ko), bo | output-layer partial dots
-__host__ __device__ inline int fz_aux_floats(const NetDims& d, int W) { return (aux_floats(d, W) + 3) / 4 * 4; }
-__host__ __device__ inline int fz_fl_floats(const NetDims& d, int WT, int S, int LM) {
-  const int W = 16 * WT;
-  const int common = fz_aux_floats(d, W) + FZ_PT * TDQ_MAXD + S * FZ_PT * 4;
-  const int part = 2 * ((LM + 1) * W + d.d_in * W + 4 * W) + 4;
-  const int outp = 4 * S * FZ_PT;
-  return common + part + outp + FZ_PT;  // + the loss's prefetched per-point input
+// The float area after the images of a PT-point-tile kernel (float offsets; host LDS sizing and the
+// kernels' carve-up both come from here):
+//   aux copy (the aux image of jet_bf3.h with n_hidden = LM + 1: K0 rows, b0, hidden biases at bh,
+//   Ko [W][4] at ko, bo at bo; rounded up to 4 floats) | xs [PT][TDQ_MAXD] | ubs [S][PT][4] dJ of the
+//   tile | part: NQ sets (one per 16-point column tile) of pq partials - biases of layers 0..LM
+//   [LM + 1][W], K0 [d_in][W], Ko [W][4] - and 4 spare floats | outp [NW waves][S][PT] output-layer
+//   partial dots | lpre [PT] the loss's prefetched per-point input
+struct FzFl {
+  int bh, ko, bo, xs, ubs, part, pq, outp, lpre, total;
+};
+__host__ __device__ constexpr FzFl fz_fl(int W, int d_in, int S, int LM, int PT, int NQ, int NW) {
+  FzFl f{};
+  f.bh = (d_in + 1) * W;
+  f.ko = (d_in + LM + 1) * W;
+  f.bo = (d_in + LM + 5) * W;
+  f.xs = (f.bo + 4 + 3) / 4 * 4;
+  f.ubs = f.xs + PT * TDQ_MAXD;
+  f.part = f.ubs + S * PT * 4;
+  f.pq = (LM + 1) * W + d_in * W + 4 * W;
+  f.outp = f.part + NQ * f.pq + 4;
+  f.lpre = f.outp + NW * S * PT;
+  f.total = f.lpre + PT;
+  return f;
 }
 __host__ __device__ inline int fz_lds_bytes(const NetDims& d, int WT, int S, int LM) {
-  return fz_img_elems(WT, S, LM) * 2 + fz_fl_floats(d, WT, S, LM) * 4;
+  return fz_img_elems(WT, S, LM) * 2 + fz_fl(16 * WT, d.d_in, S, LM, FZ_PT, 2, 4).total * 4;
 }
 
 // Layer 0 (input -> width, VALU) of feature tile t at one point x (LDS row) - computed twice per
@@ -80,13 +94,15 @@ __host__ __device__ inline int fz_lds_bytes(const NetDims& d, int WT, int S, int
 // 2.57e-2 with tanh_s1 (profiles/r5acc2_l2_six_seeds.jsonl).  In the hidden layers the cheap form
 // cost accuracy (L2 median 2.99e-2, profiles/r5acc_accuracy_ab.jsonl): they use tanh_jet_f.
 // !CHEAP (the bf16x3 objective, jet_fused3.h): tanh_s1, the saved-activation kernels' tanh.
-template <int WT, int S, int NSO, bool CHEAP = true, int DIN = 0>
-__device__ __forceinline__ void fz_h0(const JetSpec& sp, const float* aux, const NetDims& d, const float* xrow, int t,
-                                      int g, f32x4 (&h)[S]) {
+// DIN: the input width, a compile-time constant of the generated kernels (aux: K0 rows, then b0).
+template <int WT, int S, int NSO, bool CHEAP, int DIN>
+__device__ __forceinline__ void fz_h0(const JetSpec& sp, const float* aux, const float* xrow, int t, int g,
+                                      f32x4 (&h)[S]) {
   constexpr int S1 = S - 1 - NSO, SO = 1 + S1, W = 16 * WT;
+  static_assert(DIN > 0, "fz_h0: compile-time input width");
   const int f0 = 16 * t + 4 * g;
-  f32x4 z = *reinterpret_cast<const f32x4*>(aux + (DIN > 0 ? DIN * W : aux_b0(d, W)) + f0);
-  if constexpr (DIN > 0) {  // compile-time input width (the generated fused-step kernels)
+  f32x4 z = *reinterpret_cast<const f32x4*>(aux + DIN * W + f0);
+  {
     // scalar FMAs, not f32x4 arithmetic: the vector form compiles to v_pk_fma_f32 whose result
     // the next-but-one VALU reads; in the layer-0 adjoint (right after the dK_1 MFMA burst) that
     // read returned stale lanes 48-63 of component 0 on some runs - b0 / K0 gradients of every
@@ -102,8 +118,6 @@ __device__ __forceinline__ void fz_h0(const JetSpec& sp, const float* aux, const
       for (int j = 0; j < DIN; ++j) a = fmaf(x[j], aux[j * W + f0 + c], a);
       z[c] = a;
     }
-  } else {
-    for (int j = 0; j < d.d_in; ++j) z += xrow[j] * *reinterpret_cast<const f32x4*>(aux + j * W + f0);
   }
   f32x4 ka[S];
   ka[0] = zero4();
@@ -170,6 +184,15 @@ __device__ __forceinline__ f32x4 fz_bf4(bf16x4 v) {
   const u32x2 u = __builtin_bit_cast(u32x2, v);
   return f32x4{__uint_as_float(u[0] << 16), __uint_as_float(u[0] & 0xffff0000u), __uint_as_float(u[1] << 16),
                __uint_as_float(u[1] & 0xffff0000u)};
+}
+// the streams of feature tile t from a slot of the bf16 step (S hi images of FZ_PT rows, then the
+// value stream's lo image): h[0] = hi + lo, h[s] = hi (fz3_get_h of jet_fused3.h is the bf16x3 slots')
+template <int WT, int S>
+__device__ __forceinline__ void fz_get_h(const __bf16* im, const FzLane& L, int q, int t, f32x4 (&h)[S]) {
+  constexpr int RS = bf3_img_rs(WT), SIMG = FZ_PT * RS;
+  h[0] = fz_bf4(fz_get<RS>(im, L, q, t)) + fz_bf4(fz_get<RS>(im + S * SIMG, L, q, t));
+#pragma unroll
+  for (int s = 1; s < S; ++s) h[s] = fz_bf4(fz_get<RS>(im + s * SIMG, L, q, t));
 }
 
 // A fragments (hi only) of a GEMM: the wave's OPW output tiles of a weight image in global memory
@@ -245,9 +268,13 @@ __device__ __forceinline__ void fz_gemm(f32x4 (&acc)[OPW][S], FzW<WT, OPW>& w, c
 // NR x NC block of 16 x 16 output tiles at row tiles r0.., column tiles c0..).  The k index of
 // each MFMA runs over 32 image rows: 32 points of one stream here (SIMG = FZ_PT * RS); the
 // 16-point-tile kernel of jet_fused3.h passes two streams' 16-row images as one 32-row image.
-template <int WT, int S, int NR, int NC, bool SB = true, int SIMG = FZ_PT * bf3_img_rs(WT)>
-__device__ __forceinline__ void fz_dk(f32x4 (&dk)[NR][NC], const __bf16* H, const __bf16* Z, int r0, int c0, int l) {
-  constexpr int RS = bf3_img_rs(WT);
+// This lane's transposed-read bases in a 32-row image: a1 / a2 for the two reads of H's row tile r0,
+// z1 / z2 for Z's column tile c0 (tile r0 + r at + 16 r)
+struct FzTr {
+  int a1, a2, z1, z2;
+};
+template <int RS, int NR, int NC>
+__device__ __forceinline__ FzTr fz_tr(int r0, int c0, int l) {
   const int g = l >> 4;
   const int tr_row = 8 * g + ((l & 15) >> 2);
   const int swz = (g & 1) << 6;
@@ -255,9 +282,13 @@ __device__ __forceinline__ void fz_dk(f32x4 (&dk)[NR][NC], const __bf16* H, cons
   // (16 (r0 + r) + tr_col) ^ swz = ((16 r0) ^ swz) + 16 r + tr_col as long as no carry crosses
   // bit 6: blocks of 4 tiles start on multiples of 64 columns, blocks of 2 on multiples of 32 (and
   // 16 r + tr_col <= 28) - one base per read, immediates after
-  static_assert((NR == 4 || NR <= 2) && (NC == 4 || NC <= 2), "fz_dk: tile blocks of 1, 2 or 4");
-  const int a1 = tr_row * RS + tr_col1 + ((16 * r0) ^ swz), a2 = (tr_row + 4) * RS + tr_col2 + ((16 * r0) ^ swz);
-  const int z1 = tr_row * RS + tr_col1 + ((16 * c0) ^ swz), z2 = (tr_row + 4) * RS + tr_col2 + ((16 * c0) ^ swz);
+  static_assert((NR == 4 || NR <= 2) && (NC == 4 || NC <= 2), "fz_tr: tile blocks of 1, 2 or 4");
+  return FzTr{tr_row * RS + tr_col1 + ((16 * r0) ^ swz), (tr_row + 4) * RS + tr_col2 + ((16 * r0) ^ swz),
+              tr_row * RS + tr_col1 + ((16 * c0) ^ swz), (tr_row + 4) * RS + tr_col2 + ((16 * c0) ^ swz)};
+}
+template <int WT, int S, int NR, int NC, bool SB = true, int SIMG = FZ_PT * bf3_img_rs(WT)>
+__device__ __forceinline__ void fz_dk(f32x4 (&dk)[NR][NC], const __bf16* H, const __bf16* Z, int r0, int c0, int l) {
+  const auto [a1, a2, z1, z2] = fz_tr<bf3_img_rs(WT), NR, NC>(r0, c0, l);
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     bf16x8 A[NR], B[NC];
@@ -290,7 +321,6 @@ struct FzParams {
   float* slab;          // gradient-slab row blockIdx.x
   int N, Pst, ntiles;   // the tiles cover points [0, N)
   NetDims d;
-  JetSpec sp;
   // the loss program's pointer table (the generated loss maps a point to its group)
   const FzLossPtrs* lptrs;
   float* lpart;         // loss / scalar-gradient partials, row prow + blockIdx.x, nacc floats each
@@ -307,6 +337,43 @@ __device__ __forceinline__ float fz_jsum(const float* jv, int s, int k, float bo
   return s == 0 ? a + bo : a;
 }
 
+// ---- Steps of the tile loop that fz_body below (32-point tiles) and fz3_body of jet_fused3.h
+// (16-point tiles) share, beside FzFl, fz_h0, fz_tr and fz_jsum above.  The other steps the two
+// bodies have in common (the tile fetch, the accumulator zeroing, the output-layer dots and
+// adjoint, the layer-0 partials, the slab epilogue) stay written out in both: as shared functions
+// each changed the generated code of one of the kernels (profiles/r9_fused_refactor.md).
+
+// This thread's element of a PT-point tile's inputs (fetched one tile ahead) -> LDS: coordinate j
+// of point pt on thread pt * TDQ_MAXD + j, the loss's first per-point input on the PT threads after
+template <int PT>
+__device__ __forceinline__ void fz_stage(float* xs, float* lpre, int tid, float v) {
+  if (tid < PT * TDQ_MAXD) xs[tid] = v;
+  else if (tid < PT * TDQ_MAXD + PT) lpre[tid - PT * TDQ_MAXD] = v;
+}
+
+// Set-up: the aux image copied once into LDS (zero padded to NAUX floats).  Beside the copy, this
+// XCD's L2 is warmed with the weight images (bf16x3: hi and lo) before the first tile's GEMMs: the
+// workgroups of an XCD (blocks gi, gi + 8, ... when the dispatcher deals them round-robin) each
+// touch a slice (the first tile's GEMMs ran 500-800 cycles slower each without: bf16 step
+// 0.1429 -> 0.1400 ms, profiles/r6x_weight_prefetch_ab.txt)
+template <int WT, int LM, int NAUX>
+__device__ __forceinline__ void fz_setup(const FzParams& P, float* aux, int tid) {
+  const float* __restrict__ aux_g = P.aux;
+  const int G = gridDim.x, gi = blockIdx.x;
+  bf16x8 wpf[2];
+  {
+    constexpr int NI16 = LM * WT * (WT / 2) * 128 * 4 * 4 / 16;  // 16-byte granules per image
+    const int xw = gi >> 3, nx = (G + 7) >> 3;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int e = (xw + k * nx) * 64 * FZ_WAVES + tid;
+      wpf[k] = e < 2 * NI16 ? (e < NI16 ? P.fimg[e] : P.bimg[e - NI16]) : bf16x8{};
+    }
+  }
+  for (int e = tid; e < NAUX; e += 64 * FZ_WAVES) aux[e] = e < aux_floats(P.d, 16 * WT) ? aux_g[e] : 0.f;
+  asm volatile("" ::"v"(wpf[0]), "v"(wpf[1]));
+}
+
 // The generated loss (ops/fused_step.py gen_loss) has this interface:
 //   NACC: loss / scalar-gradient sums per point-thread;
 //   eval<S, PT, NW>(jv, xs, t, n, N, ptrs, ubs, acc, pv, bo) on the tile's point-thread t (point n
@@ -321,35 +388,25 @@ __device__ __forceinline__ float fz_jsum(const float* jv, int s, int k, float bo
 // every GEMM / epilogue, and owns an NR x NC block of each hidden layer's dK tiles.
 template <int WT, int S, int NSO, int LM, class LossF>
 __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
-  const float* __restrict__ X = P.X;
-  const float* __restrict__ aux_g = P.aux;
   const int N = P.N, Pst = P.Pst, ntiles = P.ntiles;
   const NetDims& d = P.d;
   // the stream spec and input width as compile-time constants of the generated loss struct
   // (ops/fused_step.py spec_source): the one-hot stream selects and first-layer loops fold away
   constexpr JetSpec sp = LossF::SPEC;
   constexpr int DIN = LossF::DIN;
-  // compile-time aux-image / LDS offsets (d_in = DIN, n_hidden = LM + 1): LDS accesses then take
-  // immediate offsets instead of runtime address arithmetic
-  constexpr int W_ = 16 * WT;
-  constexpr int A_B0 = DIN * W_, A_BH = (DIN + 1) * W_, A_KO = (DIN + LM + 1) * W_, A_BO = (DIN + LM + 5) * W_;
-  constexpr int NAUX = (A_BO + 4 + 3) / 4 * 4;           // fz_aux_floats
-  constexpr int W = 16 * WT, OPW = WT / 4, RS = bf3_img_rs(WT), SIMG = FZ_PT * RS;
+  constexpr int W = 16 * WT, OPW = WT / 4, RS = bf3_img_rs(WT), SIMG = FZ_PT * RS, PT = FZ_PT;
   constexpr int NR = WT / 4, NC = WT / 2;  // dK tiles per wave: row block (w >> 1), column block (w & 1)
   constexpr int ZS = 0;                    // slot of h_LM / zb_LM (h_0's slot once layer 1 has read it)
   static_assert(OPW >= 1 && OPW * 4 == WT, "fused step: WT = 4 or 8");
   static_assert(LM >= 2, "fused step keeps h_LM in h_0's slot");
   __bf16* img = reinterpret_cast<__bf16*>(lds_raw);
   auto slot = [&](int k) { return img + k * (S + 1) * SIMG; };
-  float* fl = reinterpret_cast<float*>(img + fz_img_elems(WT, S, LM));
-  constexpr int naux = NAUX;
-  float* aux = fl;                            // the aux image (biases, K0, Ko, bo), copied once
-  float* xs = aux + naux;                     // [FZ_PT][TDQ_MAXD]
-  float* ubs = xs + FZ_PT * TDQ_MAXD;         // [S][FZ_PT][4] dJ of the tile
-  float* part = ubs + S * FZ_PT * 4;          // [2 column tiles][...] partials
-  constexpr int pq = (LM + 1) * W + DIN * W + 4 * W;  // partial floats per column tile
-  float* outp = part + 2 * pq + 4;            // [4][S][FZ_PT] output-layer dots
-  float* lpre = outp + 4 * S * FZ_PT;         // [FZ_PT] the loss's prefetched first input
+  // compile-time aux-image / LDS offsets (d_in = DIN, n_hidden = LM + 1): LDS accesses then take
+  // immediate offsets instead of runtime address arithmetic.  Two partial sets (one per column
+  // tile), output dots of the 4 waves of a column tile
+  constexpr FzFl F = fz_fl(W, DIN, S, LM, PT, 2, 4);
+  float* aux = reinterpret_cast<float*>(img + fz_img_elems(WT, S, LM));
+  float *xs = aux + F.xs, *ubs = aux + F.ubs, *part = aux + F.part, *outp = aux + F.outp, *lpre = aux + F.lpre;
 
   const int tid = threadIdx.x, l = tid & 63, p = l & 15, g = l >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -360,9 +417,9 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   const int o0 = wo * OPW;                          // feature tiles of this wave (GEMM outputs)
   const int row = 16 * q + p;                       // this lane's point in the tile
   const FzLane L = fz_lane<RS>(p, g);
-  float* accB = part + q * pq;                      // [LM + 1][W]  bias partials (layer 0..LM)
-  float* accK0 = accB + (LM + 1) * W;               // [d_in][W]
-  float* accKo = accK0 + d.d_in * W;                // [W][4]
+  float* accB = part + q * F.pq;                    // [LM + 1][W]  bias partials (layer 0..LM)
+  float* accK0 = accB + (LM + 1) * W;               // [DIN][W]
+  float* accKo = accK0 + DIN * W;                   // [W][4]
   // Loop-invariant weight loads must not be hoisted out of the tile loop (they would pin ~100
   // VGPRs for the whole launch): the image pointers go through an opaque copy at every tile.
   const bf16x8* Wimg = P.fimg;
@@ -371,6 +428,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   // this thread's element of a tile's x (one: FZ_PT * TDQ_MAXD <= 512), fetched one tile ahead so
   // the global latency hides behind the current tile
   static_assert(FZ_PT * TDQ_MAXD + FZ_PT <= 64 * FZ_WAVES, "one element per thread");
+  const float* __restrict__ X = P.X;
   float xpre = 0.f;
   auto fetch = [&](int tt) {
     const int pb = tt * FZ_PT;
@@ -383,22 +441,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
     }
   };
   if (t0 < t1) fetch(t0);  // first, so its latency overlaps the set-up below
-  // warm this XCD's L2 with the weight images before the first tile's GEMMs: the workgroups of an
-  // XCD (blocks gi, gi + 8, ... when the dispatcher deals them round-robin) each touch a slice (the
-  // first tile's GEMMs ran 500-800 cycles slower each without: step 0.1429 -> 0.1400 ms,
-  // profiles/r6x_weight_prefetch_ab.txt)
-  bf16x8 wpf[2];
-  {
-    constexpr int NI16 = LM * WT * (WT / 2) * 128 * 4 * 4 / 16;  // 16-byte granules per image
-    const int xw = gi >> 3, nx = (G + 7) >> 3;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int e = (xw + k * nx) * 64 * FZ_WAVES + tid;
-      wpf[k] = e < 2 * NI16 ? (e < NI16 ? P.fimg[e] : P.bimg[e - NI16]) : bf16x8{};
-    }
-  }
-  for (int e = tid; e < naux; e += 64 * FZ_WAVES) aux[e] = e < aux_floats(d, W) ? aux_g[e] : 0.f;
-  asm volatile("" ::"v"(wpf[0]), "v"(wpf[1]));
+  fz_setup<WT, LM, F.xs>(P, aux, tid);
   f32x4 dk[LM][NR][NC];
   float lacc[LossF::NACC];  // this point-thread's loss / scalar-gradient sums (all tiles)
   float bo_acc = 0.f;       // this point-thread's output-bias gradient (its points' value-stream dJ)
@@ -410,22 +453,20 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
     for (int r = 0; r < NR; ++r)
 #pragma unroll
       for (int c = 0; c < NC; ++c) dk[i][r][c] = zero4();
-  for (int e = tid; e < 2 * pq + 4; e += 64 * FZ_WAVES) part[e] = 0.f;
-  const float* Ko = aux + A_KO;
+  for (int e = tid; e < 2 * F.pq + 4; e += 64 * FZ_WAVES) part[e] = 0.f;
+  const float* Ko = aux + F.ko;
 
   // layer 0 (input -> width, VALU) of feature tile o0 + oo at this lane's point
-  auto layer0 = [&](int oo, f32x4(&h)[S]) { fz_h0<WT, S, NSO, true, DIN>(sp, aux, d, xs + row * TDQ_MAXD, o0 + oo, g, h); };
-
+  auto layer0 = [&](int oo, f32x4(&h)[S]) { fz_h0<WT, S, NSO, true, DIN>(sp, aux, xs + row * TDQ_MAXD, o0 + oo, g, h); };
 
   int t = t0;
   FzW<WT, OPW> wf;  // the next GEMM's weight fragments (fz_pre_w in front of the barrier, the rest in fz_gemm)
   TDQ_TS(0);
   while (t < t1) {
-    const int pb = t * FZ_PT;
+    const int pb = t * PT;
     asm volatile("" : "+s"(Wimg), "+s"(Kimg));
     __syncthreads();  // the previous tile's readers of xs / ubs / images are done (and aux / part set)
-    if (tid < FZ_PT * TDQ_MAXD) xs[tid] = xpre;
-    else if (tid < FZ_PT * TDQ_MAXD + FZ_PT) lpre[tid - FZ_PT * TDQ_MAXD] = xpre;
+    fz_stage<PT>(xs, lpre, tid, xpre);
     if (t + 1 < t1) fetch(t + 1);
     __syncthreads();
     FZ_TS(1);
@@ -445,7 +486,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
     // ---- hidden layers 1..LM on MFMA ------------------------------------------------------
 #pragma unroll
     for (int ly = 1; ly <= LM; ++ly) {
-      const float* bi = aux + A_BH + (ly - 1) * W;
+      const float* bi = aux + F.bh + (ly - 1) * W;
       f32x4 acc[OPW][S];
       fz_gemm<WT, S, OPW>(acc, wf, Wimg, ly, o0, l, slot(ly - 1), q, L);
       FZ_TS(1 + 2 * ly);
@@ -495,23 +536,21 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
     // fewer, 0.1383 -> 0.1376 ms, profiles/r6ag_jsum_ab.txt)
     int tl = tid;
     asm volatile("" : "+v"(tl));
-    if (tl < FZ_PT) LossF::template eval<S, FZ_PT, 4>(outp, xs, tl, pb + tl, N, *P.lptrs, ubs, lacc, lpre[tl], aux[A_BO]);
+    if (tl < PT) LossF::template eval<S, PT, 4>(outp, xs, tl, pb + tl, N, *P.lptrs, ubs, lacc, lpre[tl], aux[F.bo]);
     __syncthreads();
     FZ_TS(9);
     // dbo: each point-thread adds its point's value-stream dJ (one LDS read; a 32-step loop on
     // four lanes of wave 0 used to hold that wave - and the next barrier - for ~1-2k cycles)
     tl = tid;
     asm volatile("" : "+v"(tl));
-    if (tl < FZ_PT) bo_acc += ubs[tl * 4];
+    if (tl < PT) bo_acc += ubs[tl * 4];
     // ---- reverse through the output layer: hb = Ko ub, dKo, the top tanh layer's adjoint ----
 #pragma unroll
     for (int oo = 0; oo < OPW; ++oo) {
       const int to = o0 + oo;
       __bf16* im = slot(ZS);
       f32x4 h[S], hb[S], zb[S];
-      h[0] = fz_bf4(fz_get<RS>(im, L, q, to)) + fz_bf4(fz_get<RS>(im + S * SIMG, L, q, to));
-#pragma unroll
-      for (int s = 1; s < S; ++s) h[s] = fz_bf4(fz_get<RS>(im + s * SIMG, L, q, to));
+      fz_get_h<WT, S>(im, L, q, to, h);
       f32x4 kq, pp = zero4();
 #pragma unroll
       for (int c = 0; c < 4; ++c) kq[c] = Ko[(16 * to + 4 * g + c) * 4];
@@ -551,9 +590,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
         for (int oo = 0; oo < OPW; ++oo) {
           const int to = o0 + oo;
           f32x4 h[S], zb[S];
-          h[0] = fz_bf4(fz_get<RS>(H, L, q, to)) + fz_bf4(fz_get<RS>(H + S * SIMG, L, q, to));
-#pragma unroll
-          for (int s = 1; s < S; ++s) h[s] = fz_bf4(fz_get<RS>(H + s * SIMG, L, q, to));
+          fz_get_h<WT, S>(H, L, q, to, h);
           tanh_jet_b<S, NSO>(sp, h, acc[oo], zb);
           rb[oo] = row16_sum4(zb[0]);
 #pragma unroll
@@ -579,9 +616,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
         for (int oo = 0; oo < OPW; ++oo) {
           const int to = o0 + oo;
           f32x4 h[S], zb[S];
-          h[0] = fz_bf4(fz_get<RS>(H, L, q, to)) + fz_bf4(fz_get<RS>(H + S * SIMG, L, q, to));
-#pragma unroll
-          for (int s = 1; s < S; ++s) h[s] = fz_bf4(fz_get<RS>(H + s * SIMG, L, q, to));
+          fz_get_h<WT, S>(H, L, q, to, h);
           tanh_jet_b<S, NSO>(sp, h, acc[oo], zb);
           const int fo = 16 * to + 4 * g + (p >> 2);
           {
@@ -651,17 +686,17 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   }
   __syncthreads();  // LDS partials complete
   const float* pA = part;
-  const float* pB = part + pq;
+  const float* pB = part + F.pq;
   for (int f = tid; f < W; f += 64 * FZ_WAVES) {
-    gs[d.d_in * W + f] = (__bf16)(pA[f] + pB[f]);  // b0
+    gs[DIN * W + f] = (__bf16)(pA[f] + pB[f]);  // b0
     for (int ly = 1; ly <= LM; ++ly)
       gs[off_layer(d, ly) + W * W + f] = (__bf16)(pA[ly * W + f] + pB[ly * W + f]);
-    for (int j = 0; j < d.d_in; ++j) {
+    for (int j = 0; j < DIN; ++j) {
       const int k = (LM + 1) * W + j * W + f;
       gs[j * W + f] = (__bf16)(pA[k] + pB[k]);
     }
     for (int qo = 0; qo < d.d_out; ++qo) {
-      const int k = (LM + 1 + d.d_in) * W + f * 4 + qo;
+      const int k = (LM + 1 + DIN) * W + f * 4 + qo;
       gs[off_layer(d, LM + 1) + f * d.d_out + qo] = (__bf16)(pA[k] + pB[k]);
     }
   }

@@ -33,15 +33,9 @@ __host__ __device__ constexpr int fz3_vrs() { return 132; }  // fp32 value image
 __host__ __device__ constexpr int fz3_slot_bytes(int WT, int S) {
   return 2 * fz3_sp(S) * FZ3_PT * bf3_img_rs(WT) * 2 + FZ3_PT * fz3_vrs() * 4;
 }
-// float area after the slots: aux copy | xs | ubs | partials (biases of layers 0..LM, K0, Ko), bo |
-// output-layer partial dots [8 waves][S][FZ3_PT]
-__host__ __device__ inline int fz3_fl_floats(const NetDims& d, int WT, int S, int LM) {
-  const int W = 16 * WT;
-  return fz_aux_floats(d, W) + FZ3_PT * TDQ_MAXD + S * FZ3_PT * 4 + ((LM + 1) * W + d.d_in * W + 4 * W) + 4 +
-         FZ_WAVES * S * FZ3_PT + FZ3_PT;  // + the loss's prefetched per-point input
-}
+// float area after the slots (FzFl): one set of partials, output-layer partial dots of 8 waves
 __host__ __device__ inline int fz3_lds_bytes(const NetDims& d, int WT, int S, int LM) {
-  return fz_nslot(LM) * fz3_slot_bytes(WT, S) + fz3_fl_floats(d, WT, S, LM) * 4;
+  return fz_nslot(LM) * fz3_slot_bytes(WT, S) + fz_fl(16 * WT, d.d_in, S, LM, FZ3_PT, 1, FZ_WAVES).total * 4;
 }
 
 // A fragments (hi + lo, every k-block) of one GEMM's weight-image rows.  In use: all issued at the
@@ -99,12 +93,7 @@ __device__ __forceinline__ void fz3_gemm(f32x4 (&acc)[S], const Fz3W<WT>& w, con
 template <int WT, int S, int NR, int NC>
 __device__ __forceinline__ void fz3_dk(f32x4 (&dk)[NR][NC], const __bf16* H, const __bf16* Z, int r0, int c0, int l) {
   constexpr int RS = bf3_img_rs(WT), SIMG = FZ3_PT * RS, SP = fz3_sp(S);
-  const int g = l >> 4;
-  const int tr_row = 8 * g + ((l & 15) >> 2);
-  const int swz = (g & 1) << 6;
-  const int tr_col1 = 4 * ((l & 3) ^ ((2 * g) & 3)), tr_col2 = 4 * ((l & 3) ^ ((2 * g + 1) & 3));
-  const int a1 = tr_row * RS + tr_col1 + ((16 * r0) ^ swz), a2 = (tr_row + 4) * RS + tr_col2 + ((16 * r0) ^ swz);
-  const int z1 = tr_row * RS + tr_col1 + ((16 * c0) ^ swz), z2 = (tr_row + 4) * RS + tr_col2 + ((16 * c0) ^ swz);
+  const auto [a1, a2, z1, z2] = fz_tr<RS, NR, NC>(r0, c0, l);
 #pragma unroll
   for (int pr = 0; pr < SP / 2; ++pr) {
     const __bf16* Hh = H + 2 * pr * SIMG;
@@ -161,19 +150,12 @@ __device__ __forceinline__ void fz3_get_h(const __bf16* slot, const FzLane& L, i
 
 template <int WT, int S, int NSO, int LM, class LossF>
 __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
-  const float* __restrict__ X = P.X;
-  const float* __restrict__ aux_g = P.aux;
   const int N = P.N, Pst = P.Pst, ntiles = P.ntiles;
   const NetDims& d = P.d;
   // the stream spec and input width as compile-time constants of the generated loss struct
   // (ops/fused_step.py spec_source): the one-hot stream selects and first-layer loops fold away
   constexpr JetSpec sp = LossF::SPEC;
   constexpr int DIN = LossF::DIN;
-  // compile-time aux-image / LDS offsets (d_in = DIN, n_hidden = LM + 1): LDS accesses then take
-  // immediate offsets instead of runtime address arithmetic
-  constexpr int W_ = 16 * WT;
-  constexpr int A_B0 = DIN * W_, A_BH = (DIN + 1) * W_, A_KO = (DIN + LM + 1) * W_, A_BO = (DIN + LM + 5) * W_;
-  constexpr int NAUX = (A_BO + 4 + 3) / 4 * 4;           // fz_aux_floats
   constexpr int W = 16 * WT, RS = bf3_img_rs(WT), SIMG = FZ3_PT * RS, SP = fz3_sp(S), VRS = fz3_vrs();
   constexpr int NR = WT / 4, NC = WT / 2;  // dK tiles per wave: row block (w >> 1), column block (w & 1)
   constexpr int SLOT = fz3_slot_bytes(WT, S), PT = FZ3_PT;
@@ -181,15 +163,10 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
   static_assert(LM >= 2, "bf16x3 fused step keeps h_LM in h_0's slot");
   static_assert(SLOT % 16 == 0, "slot alignment");
   auto slot = [&](int k) { return reinterpret_cast<__bf16*>(lds_raw + k * SLOT); };
-  float* fl = reinterpret_cast<float*>(lds_raw + fz_nslot(LM) * SLOT);
-  constexpr int naux = NAUX;
-  float* aux = fl;                            // the aux image (biases, K0, Ko, bo), copied once
-  float* xs = aux + naux;                     // [PT][TDQ_MAXD]
-  float* ubs = xs + PT * TDQ_MAXD;            // [S][PT][4] dJ of the tile
-  float* part = ubs + S * PT * 4;             // partials
-  constexpr int pq = (LM + 1) * W + DIN * W + 4 * W;
-  float* outp = part + pq + 4;                // [8 waves][S][PT] output-layer dots
-  float* lpre = outp + FZ_WAVES * S * PT;     // [PT] the loss's prefetched first input
+  // compile-time aux-image / LDS offsets, as fz_body: one partial set, output dots of all 8 waves
+  constexpr FzFl F = fz_fl(W, DIN, S, LM, PT, 1, FZ_WAVES);
+  float* aux = reinterpret_cast<float*>(lds_raw + fz_nslot(LM) * SLOT);
+  float *xs = aux + F.xs, *ubs = aux + F.ubs, *part = aux + F.part, *outp = aux + F.outp, *lpre = aux + F.lpre;
 
   const int tid = threadIdx.x, l = tid & 63, p = l & 15, g = l >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -200,11 +177,14 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
   const FzLane L = fz_lane<RS>(p, g);
   const int voff = p * VRS + 16 * o + 4 * g;        // this lane's f32x4 in a value image
   float* accB = part;                               // [LM + 1][W]  bias partials (layer 0..LM)
-  float* accK0 = accB + (LM + 1) * W;               // [d_in][W]
-  float* accKo = accK0 + d.d_in * W;                // [W][4]
+  float* accK0 = accB + (LM + 1) * W;               // [DIN][W]
+  float* accKo = accK0 + DIN * W;                   // [W][4]
   const bf16x8* Wimg = P.fimg;
   const bf16x8* Kimg = P.bimg;
 
+  // this thread's element of a tile's x / loss input, fetched one tile ahead (as fz_body)
+  static_assert(PT * TDQ_MAXD + PT <= 64 * FZ_WAVES, "one element per thread");
+  const float* __restrict__ X = P.X;
   float xpre = 0.f;
   auto fetch = [&](int tt) {
     const int pb = tt * PT;
@@ -217,20 +197,8 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     }
   };
   if (t0 < t1) fetch(t0);  // first, so its latency overlaps the set-up below
-  // this XCD's L2 warmed with the weight images (hi and lo) before the first tile (as fz_body)
-  bf16x8 wpf[2];
-  {
-    constexpr int NI16 = LM * WT * (WT / 2) * 128 * 4 * 4 / 16;  // 16-byte granules per image
-    const int xw = gi >> 3, nx = (G + 7) >> 3;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int e = (xw + k * nx) * 64 * FZ_WAVES + tid;
-      wpf[k] = e < 2 * NI16 ? (e < NI16 ? P.fimg[e] : P.bimg[e - NI16]) : bf16x8{};
-    }
-  }
-  for (int e = tid; e < naux; e += 64 * FZ_WAVES) aux[e] = e < aux_floats(d, W) ? aux_g[e] : 0.f;
-  asm volatile("" ::"v"(wpf[0]), "v"(wpf[1]));
-  for (int e = tid; e < pq + 4; e += 64 * FZ_WAVES) part[e] = 0.f;
+  fz_setup<WT, LM, F.xs>(P, aux, tid);
+  for (int e = tid; e < F.pq + 4; e += 64 * FZ_WAVES) part[e] = 0.f;
   if constexpr (SP != S) {  // the padding stream's images (hi, lo) of every slot stay zero
     for (int k = 0; k < fz_nslot(LM); ++k)
       for (int e = tid; e < SIMG; e += 64 * FZ_WAVES) {
@@ -249,12 +217,10 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     for (int r = 0; r < NR; ++r)
 #pragma unroll
       for (int c = 0; c < NC; ++c) dk[i][r][c] = zero4();
-  const float* Ko = aux + A_KO;
+  const float* Ko = aux + F.ko;
 
   // layer 0 (input -> width, VALU; the accurate tanh) of this wave's feature tile at this lane's point
-  auto layer0 = [&](f32x4(&h)[S]) { fz_h0<WT, S, NSO, false, DIN>(sp, aux, d, xs + p * TDQ_MAXD, o, g, h); };
-
-  static_assert(PT * TDQ_MAXD <= 64 * FZ_WAVES, "one element per thread");
+  auto layer0 = [&](f32x4(&h)[S]) { fz_h0<WT, S, NSO, false, DIN>(sp, aux, xs + p * TDQ_MAXD, o, g, h); };
 
   int t = t0;
   Fz3W<WT> wf;  // a GEMM's weight fragments
@@ -263,8 +229,7 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     const int pb = t * PT;
     asm volatile("" : "+s"(Wimg), "+s"(Kimg));
     __syncthreads();  // the previous tile's readers of xs / ubs / images are done (and aux / part set)
-    if (tid < PT * TDQ_MAXD) xs[tid] = xpre;
-    else if (tid < PT * TDQ_MAXD + PT) lpre[tid - PT * TDQ_MAXD] = xpre;
+    fz_stage<PT>(xs, lpre, tid, xpre);
     if (t + 1 < t1) fetch(t + 1);
     __syncthreads();
     FZ_TS(1);
@@ -281,7 +246,7 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     // ---- hidden layers 1..LM on MFMA ------------------------------------------------------
 #pragma unroll
     for (int ly = 1; ly <= LM; ++ly) {
-      const float* bi = aux + A_BH + (ly - 1) * W;
+      const float* bi = aux + F.bh + (ly - 1) * W;
       f32x4 z[S], h[S];
       fz3_load_w<WT>(wf, Wimg, ly, o, l);
       fz3_gemm<WT, S>(z, wf, slot(ly - 1), L);
@@ -312,10 +277,10 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     asm volatile("" : "+v"(tl));
     if (tl < S * PT) {
       const int s = tl / PT, pt = tl - s * PT;
-      float a = outp[s * PT + pt];
+      float a = outp[s * PT + pt];  // (fz_jsum, inline: the call reordered this kernel's schedule)
 #pragma unroll
       for (int ww = 1; ww < FZ_WAVES; ++ww) a += outp[(ww * S + s) * PT + pt];
-      outp[s * PT + pt] = s == 0 ? a + aux[A_BO] : a;
+      outp[s * PT + pt] = s == 0 ? a + aux[F.bo] : a;
     }
     __syncthreads();
     // ---- the per-point loss (generated) and its reverse sweep -> dJ into ubs ---------------
@@ -443,10 +408,10 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
   }
   __syncthreads();  // LDS partials complete
   for (int f = tid; f < W; f += 64 * FZ_WAVES) {
-    gs[d.d_in * W + f] = part[f];  // b0
+    gs[DIN * W + f] = part[f];  // b0
     for (int ly = 1; ly <= LM; ++ly) gs[off_layer(d, ly) + W * W + f] = part[ly * W + f];
-    for (int j = 0; j < d.d_in; ++j) gs[j * W + f] = part[(LM + 1) * W + j * W + f];
-    gs[off_layer(d, LM + 1) + f] = part[(LM + 1 + d.d_in) * W + f * 4];
+    for (int j = 0; j < DIN; ++j) gs[j * W + f] = part[(LM + 1) * W + j * W + f];
+    gs[off_layer(d, LM + 1) + f] = part[(LM + 1 + DIN) * W + f * 4];
   }
   // the output bias and the loss partials: the point-threads (wave 0, lanes < PT) summed
   if (w == 0) {

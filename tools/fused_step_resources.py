@@ -1,9 +1,12 @@
 """Register / LDS / spill report of the generated fused-step kernels (bf16 step and bf16x3
-objective) for the AC-SA program, compiled offline with hipcc for gfx950 (no GPU needed):
+objective) for the AC-SA program, compiled offline with hipcc for gfx950 (no GPU needed), each
+with the options it runs with (``fused_step._opts``: the bf16x3 kernel's differ):
 
     python tools/fused_step_resources.py [--out DIR]
 
-Prints hipcc's kernel-resource-usage remarks (VGPRs, AGPRs, spills, LDS, occupancy)."""
+Prints hipcc's kernel-resource-usage remarks (VGPRs, AGPRs, spills, LDS, occupancy) and leaves the
+source (``.hip``) and its assembly (``.s``) in DIR; ``diff`` two DIRs' ``.s`` (without their
+``__hip_cuid`` lines) to see whether a header change altered a kernel."""
 import argparse
 import os
 import subprocess
@@ -27,6 +30,7 @@ def sources():
 
 
 def main():
+    from tensordiffeq_amd.ops import fused_step
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="/tmp/fused_step_src")
     a = ap.parse_args()
@@ -35,8 +39,8 @@ def main():
         path = os.path.join(a.out, f"fused_step_{name}.hip")
         with open(path, "w") as f:
             f.write(src.replace('extern "C" __global__', '#include <hip/hip_runtime.h>\nextern "C" __global__', 1))
-        r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize",
-                            "-munsafe-fp-atomics", "--cuda-device-only", "-c", path, "-o", path + ".o",
+        r = subprocess.run(["hipcc", "--offload-arch=gfx950"] + fused_step._opts(src).split() +
+                           ["--cuda-device-only", "-S", path, "-o", path[:-4] + ".s",
                             "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
         print(f"== {name} (rc {r.returncode})")
         for ln in r.stderr.splitlines():
