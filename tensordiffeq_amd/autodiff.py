@@ -28,6 +28,15 @@ falls back to the autograd backend on any exception or mismatch (VERDICT r2 item
 * :class:`JetContext` (fast path): ``u_model(...)`` returns the precomputed jet value stream and
   ``tdq.grad`` returns the precomputed derivative stream, so the residual costs only elementwise
   torch ops on top of one fused jet evaluation (torch or HIP kernels, :mod:`.ops.jet_mlp`).
+
+Networks with several outputs (systems of PDEs): the jet carries every stream of every output, so a
+plan stays a set of multi-indices, and every registered tensor carries ``(multi-index, summed, output
+columns)``.  ``u_model(...)`` returns a :class:`_StreamTensor`; ``h[:, k:k+1]``, ``h[..., k:k+1]``,
+``h[:, k]``, ``torch.split(h, 1, dim=1)`` / ``h.split(1, 1)`` and ``torch.unbind(h, dim=1)`` of it
+are registered with the columns they pick (:func:`_select`), and ``grad`` serves those columns of the
+derivative stream, summed when there are several (``tf.gradients`` semantics).  Whatever else is done
+to a multi-column value (fancy indexing, arithmetic) yields a plain tensor the contexts do not know:
+``grad`` of it makes the planning pass choose the autograd backend, as before.
 """
 from __future__ import annotations
 
@@ -142,18 +151,106 @@ def _autograd(y, x):
     return g
 
 
+class _StreamTensor(torch.Tensor):
+    """A derivative stream of a network with several outputs (``d_out > 1``), as the contexts hand
+    it to the user's callable.  Picking output columns from it (:func:`_select`) gives another
+    registered stream; every other operation runs as plain torch and returns plain tensors, which
+    the contexts do not know (``grad`` of those is not served from the jet)."""
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        with torch._C.DisableTorchFunctionSubclass():
+            out = func(*args, **kwargs)
+        ctx = _current()
+        if ctx is not None and args and isinstance(args[0], _StreamTensor):
+            info = ctx.lookup(args[0])
+            if info is not None:
+                name = getattr(func, "__name__", "")
+                if name in ("__getitem__", "split", "unbind", "reshape", "view", "unsqueeze"):
+                    out = _select(ctx, name, args, kwargs, info, out)
+        return out
+
+
+def _col_index(idx, lo, hi):
+    """Output columns ``(lo', hi')`` that ``h[idx]`` picks from a 2-d stream holding the columns
+    ``[lo, hi)``: ``h[:, a:b]``, ``h[..., a:b]``, ``h[:, k]``, ``h[..., k]`` - else ``None``."""
+    if not (isinstance(idx, tuple) and len(idx) == 2):
+        return None
+    rows, col = idx
+    if not (rows is Ellipsis or (isinstance(rows, slice) and rows == slice(None))):
+        return None
+    n = hi - lo
+    if isinstance(col, slice):
+        if col.step not in (None, 1) or not all(v is None or type(v) is int for v in (col.start, col.stop)):
+            return None
+        a, b, _ = col.indices(n)
+        return (lo + a, lo + b) if b > a else None
+    if type(col) is int and -n <= col < n:
+        return lo + col % n, lo + col % n + 1
+    return None
+
+
+def _select(ctx, name, args, kwargs, info, out):
+    """Register the result of a column selection on the registered stream ``args[0]`` (``out``: what
+    torch computed); anything that is not one of the supported selections is returned unregistered."""
+    mi, summed, (lo, hi) = info
+    h = args[0]
+
+    def reg(t, a, b):
+        t = t.as_subclass(_StreamTensor)
+        ctx.register(t, mi, summed, (a, b))
+        return t
+
+    if name in ("reshape", "view", "unsqueeze"):
+        # a single column laid out as (n,) or (n, 1): the same stream
+        if hi - lo == 1 and torch.is_tensor(out) and out.numel() == h.numel() and out.dim() <= 2 \
+                and (out.dim() < 2 or out.shape[1] == 1):
+            return reg(out, lo, hi)
+        return out
+    if h.dim() != 2 or h.shape[1] != hi - lo:
+        return out
+    if name == "__getitem__":
+        cols = _col_index(args[1], lo, hi) if len(args) == 2 else None
+        return reg(out, *cols) if cols is not None else out
+    rest = list(args[1:])
+    if name == "split":
+        dim = kwargs.get("dim", rest[1] if len(rest) > 1 else 0)
+    else:
+        dim = kwargs.get("dim", rest[0] if rest else 0)
+    if type(dim) is not int or dim not in (1, -1) or not isinstance(out, (tuple, list)):
+        return out
+    res, a = [], lo
+    for piece in out:
+        w = piece.shape[1] if piece.dim() == 2 else 1
+        res.append(reg(piece, a, a + w))
+        a += w
+    return tuple(res) if a == hi else out
+
+
 class _Ctx:
     def __init__(self, columns):
         self.var_of = {id(c): i for i, c in enumerate(columns)}
         self._reg = {}
         self._keep = []
 
-    def register(self, t, mi, summed):
-        self._reg[id(t)] = (tuple(mi), bool(summed))
+    def register(self, t, mi, summed, cols=(0, 1)):
+        """``t`` is derivative stream ``mi`` of the output columns ``[cols[0], cols[1])`` (summed over
+        them when ``summed``)."""
+        self._reg[id(t)] = (tuple(mi), bool(summed), (int(cols[0]), int(cols[1])))
         self._keep.append(t)
 
     def lookup(self, t):
         return self._reg.get(id(t))
+
+    def _value(self, out):
+        """The network output as the callable sees it: registered with all its columns, and for
+        several outputs a :class:`_StreamTensor`, so that column selections stay streams."""
+        d_out = out.shape[1]
+        if d_out > 1:
+            out = out.as_subclass(_StreamTensor)
+        self.register(out, (), False, (0, d_out))
+        return out
 
     def accepts_cotangent(self, y, go):
         """``torch.autograd.grad(y, x, go)`` equals ``tdq.grad(y, x)`` when ``go`` is all ones
@@ -199,8 +296,7 @@ class RecordContext(_Ctx):
                 self.jetable = False
                 self.reasons.append("u_model called on inputs other than the coordinate columns")
             self.d_out = out.shape[1]
-            self.register(out, (), False)
-            return out
+            return self._value(out)
         return u_model
 
     def grad(self, y, x):
@@ -211,10 +307,10 @@ class RecordContext(_Ctx):
             self.jetable = False
             self.reasons.append("grad() of a tensor that is not a derivative stream of u_model")
             return g
-        mi, summed = info
+        mi, summed, cols = info
         mi2 = tuple(sorted(mi + (var,)))
-        summed = summed or (self.d_out or 1) > 1
-        self.register(g, mi2, summed)
+        summed = summed or cols[1] - cols[0] > 1
+        self.register(g, mi2, summed, cols)
         self.requests.add(mi2)
         return g
 
@@ -228,9 +324,7 @@ class JetContext(_Ctx):
 
     def proxy(self):
         def u_model(*args, **kw):
-            out = self.jet[()]
-            self.register(out, (), False)
-            return out
+            return self._value(self.jet[()])
         return u_model
 
     def grad(self, y, x):
@@ -238,15 +332,17 @@ class JetContext(_Ctx):
         var = self.var_of.get(id(x))
         if info is None or var is None:
             raise NotJetable("grad() of a tensor that is not a derivative stream of u_model")
-        mi, summed = info
+        mi, summed, cols = info
         mi2 = tuple(sorted(mi + (var,)))
         t = self.jet.get(mi2)
         if t is None:
             raise JetMiss(str(mi2))
+        if cols != (0, t.shape[1]):
+            t = t[:, cols[0]:cols[1]]
         if summed or t.shape[1] > 1:
             t = t.sum(dim=1, keepdim=True)
             summed = True
-        self.register(t, mi2, summed)
+        self.register(t, mi2, summed, cols)
         return t
 
 

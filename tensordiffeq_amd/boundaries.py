@@ -80,15 +80,37 @@ class BC:
             vals.append(np.broadcast_to(out, (grid.shape[0],)) if np.ndim(out) == 0 else out)
         return np.reshape(np.concatenate([np.reshape(v, (-1,)) for v in vals]), (-1, 1))
 
+    def _targets(self, funs, func_inputs, n_points):
+        """Target values of ``k`` functions: ``(n, 1)`` for one function, ``(n, k)`` - function ``q``
+        in column ``q``, the target of output ``q`` of a network with several outputs - for ``k``
+        functions over the condition's ``n`` points (the concatenated :meth:`_eval_funs` result,
+        reshaped).  Anything else stays concatenated and is refused at compile."""
+        val = self._eval_funs(funs, func_inputs)
+        k = len(func_inputs)
+        if k > 1 and val.shape[0] == k * n_points:
+            val = np.ascontiguousarray(val.reshape(k, n_points).T)
+        return val
+
+
+def _outputs(outputs):
+    """``outputs=`` of a value condition: ``None`` (every output) or a list of output columns."""
+    if outputs is None:
+        return None
+    cols = [outputs] if isinstance(outputs, (int, np.integer)) else list(outputs)
+    if not cols or any(not isinstance(c, (int, np.integer)) or c < 0 for c in cols) or len(set(cols)) != len(cols):
+        raise ValueError(f"outputs must be an output column or a list of distinct output columns, got {outputs!r}")
+    return [int(c) for c in cols]
+
 
 class dirichletBC(BC):
     kind = "dirichlet"
     isDirichlect = True
 
-    def __init__(self, domain, val, var, target):
+    def __init__(self, domain, val, var, target, outputs=None):
         if target not in ("upper", "lower"):
             raise ValueError("target must be 'upper' or 'lower'")
         self.domain, self.val, self.var, self.target_name = domain, val, var, target
+        self.outputs = _outputs(outputs)
         self.target = domain.get_dict(var)[var + target]
         self.input = self._face_mesh(var, self.target)
 
@@ -97,14 +119,15 @@ class FunctionDirichletBC(BC):
     kind = "dirichlet"
     isDirichlect = True
 
-    def __init__(self, domain, fun, var, target, func_inputs, n_values=None, replace=True):
+    def __init__(self, domain, fun, var, target, func_inputs, n_values=None, replace=True, outputs=None):
         self.domain, self.fun, self.var, self.target_name = domain, list(fun), var, target
         self.func_inputs, self.n_values = func_inputs, n_values
+        self.outputs = _outputs(outputs)
         self.targets = domain.get_dict(var)[var + target]
         mesh = self._face_mesh(var, self.targets)
         self.nums = _subset(len(mesh), n_values, replace)
         self.input = mesh if self.nums is None else mesh[self.nums]
-        val = self._eval_funs(self.fun, func_inputs)
+        val = self._targets(self.fun, func_inputs, len(mesh))
         self.val = val if self.nums is None else val[self.nums]
 
 
@@ -112,10 +135,11 @@ class IC(BC):
     kind = "ic"
     isInit = True
 
-    def __init__(self, domain, fun, var, n_values=None, replace=True, t0=None):
+    def __init__(self, domain, fun, var, n_values=None, replace=True, t0=None, outputs=None):
         if domain.time_var is None:
             raise ValueError("IC needs a domain declared with time_var")
         self.domain, self.fun, self.vars, self.n_values = domain, list(fun), var, n_values
+        self.outputs = _outputs(outputs)
         tv = domain.time_var
         self.t0 = domain.get_dict(tv)["range"][0] if t0 is None else float(t0)
         others = [v for v in domain.vars if v != tv]
@@ -123,7 +147,7 @@ class IC(BC):
         mesh = np.insert(mesh, domain.vars.index(tv), np.full(mesh.shape[0], self.t0), axis=1)
         self.nums = _subset(len(mesh), n_values, replace)
         self.input = mesh if self.nums is None else mesh[self.nums]
-        val = self._eval_funs(self.fun, var)
+        val = self._targets(self.fun, var, len(mesh))
         self.val = val if self.nums is None else val[self.nums]
 
 

@@ -10,8 +10,10 @@
 //   seeds     adj[f] += 2 c w f ; adj[w] += c f^2
 //   reverse   adjoints through every op; STREAM -> dJ[stream][point], LAM -> dlam[k][i],
 //             SCAL -> block-reduced gradient of a scalar parameter
-//   zeros     dJ of every (point, stream) the program does not read is written as 0, so dJ
-//             needs no separate memset.
+//   zeros     dJ of every (point, stream, output) the program does not read is written as 0, so
+//             dJ needs no separate memset.
+// Networks with d_out outputs (<= 4): J and dJ are [stream][point][output], and a STREAM
+// instruction's last operand is stream | output << LF_COL_SHIFT (the stream alone for one output).
 // Block partials (losses, scalar grads) are reduced by a second kernel in fixed order
 // (bitwise deterministic), which also writes the total loss.
 #include "common.h"
@@ -23,6 +25,8 @@
 #define LF_MAX_LAM 8
 #define LF_MAX_SCAL 8
 #define LF_MAX_TERMS 32
+#define LF_MAX_DOUT 4
+#define LF_COL_SHIFT 8
 
 enum {
   OP_STREAM = 1, OP_COORD = 2, OP_VAL = 3, OP_CONST = 4, OP_LAM = 5, OP_SCAL = 6,
@@ -34,7 +38,8 @@ struct LFGroup {
   int code_off, n_code, const_off, n_regs;
   int n, block_off, out_off, n_out;
   int n_slots, seg_off[LF_MAX_SLOTS];
-  unsigned loaded[LF_MAX_SLOTS];  // bit s set: stream s of that slot is read by the program
+  // bit s * d_out + q set: output q of stream s of that slot is read by the program
+  unsigned loaded[LF_MAX_SLOTS];
   // instances start `phase` threads into the group's first block: single-segment groups put their
   // block boundaries on absolute point indices that are multiples of LF_BLOCK, so point-range
   // launches of the jet kernels (multiples of 128) cut the loss blocks cleanly
@@ -56,7 +61,7 @@ struct LFPtrs {
 };
 
 struct LFMeta {
-  int n_groups, n_terms, n_scal, S, d_in, N;
+  int n_groups, n_terms, n_scal, S, d_in, N, d_out;
 };
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
@@ -100,6 +105,11 @@ __global__ void __launch_bounds__(LF_BLOCK) loss_fused_kernel(const int4* __rest
   float* V = lds;                               // [n_regs][LF_BLOCK]
   float* A = lds + G.n_regs * LF_BLOCK;         // [n_regs][LF_BLOCK]
   const int NP = meta.N;
+  const int D = meta.d_out;
+  // element (stream | output << LF_COL_SHIFT, point) of J / dJ
+  auto jidx = [&](int sw, int p) {
+    return ((size_t)(sw & ((1 << LF_COL_SHIFT) - 1)) * NP + p) * D + (sw >> LF_COL_SHIFT);
+  };
   const int nslot_acc = meta.n_terms + meta.n_scal;
   if (tid < nslot_acc) acc[tid] = 0.f;
 
@@ -108,7 +118,7 @@ __global__ void __launch_bounds__(LF_BLOCK) loss_fused_kernel(const int4* __rest
     const int4 in = code[G.code_off + pc];
     float v;
     switch (in.x) {
-      case OP_STREAM: v = J[(size_t)in.w * NP + seg_off(in.z) + ii]; break;
+      case OP_STREAM: v = J[jidx(in.w, seg_off(in.z) + ii)]; break;
       case OP_COORD: v = X[(size_t)(seg_off(in.z) + ii) * meta.d_in + in.w]; break;
       case OP_VAL: v = ptr.val[in.z][ii]; break;
       case OP_CONST: v = consts[G.const_off + in.z]; break;
@@ -158,7 +168,7 @@ __global__ void __launch_bounds__(LF_BLOCK) loss_fused_kernel(const int4* __rest
     const float g = A[in.y * LF_BLOCK + tid];
     switch (in.x) {
       case OP_STREAM:
-        if (active) dJ[(size_t)in.w * NP + seg_off(in.z) + i] = g;
+        if (active) dJ[jidx(in.w, seg_off(in.z) + i)] = g;
         break;
       case OP_LAM:
         if (active) ptr.dlam[in.z][i] = g;
@@ -220,8 +230,9 @@ __global__ void __launch_bounds__(LF_BLOCK) loss_fused_kernel(const int4* __rest
   if (active) {
     for (int sl = 0; sl < G.n_slots; ++sl) {
       const unsigned ld = sl == 0 ? G.loaded[0] : G.loaded[1];
-      for (int s = 0; s < meta.S; ++s)
-        if (!((ld >> s) & 1u)) dJ[(size_t)s * NP + seg_off(sl) + i] = 0.f;
+      for (int s = 0, bit = 0; s < meta.S; ++s)
+        for (int q = 0; q < D; ++q, ++bit)
+          if (!((ld >> bit) & 1u)) dJ[((size_t)s * NP + seg_off(sl) + i) * D + q] = 0.f;
     }
   }
 
@@ -281,10 +292,12 @@ extern "C" {
 // blocks [blk0, blk0 + nblk) only (a range launch: dJ / dlam / partials of those blocks); the
 // reduction is left to the fused step tail
 int tdq_loss_fused_range(const int* code, const float* consts, const void* outs, const void* groups,
-                         const void* ptrs, int n_groups, int n_terms, int n_scal, int S, int d_in, int N,
+                         const void* ptrs, int n_groups, int n_terms, int n_scal, int S, int d_in, int N, int d_out,
                          const float* J, const float* X, float* dJ, float* partials, int n_blocks, int blk0, int nblk,
                          int max_regs, void* stream) {
-  LFMeta meta{n_groups, n_terms, n_scal, S, d_in, N};
+  LFMeta meta{n_groups, n_terms, n_scal, S, d_in, N, d_out};
+  // the groups' `loaded` masks hold S * d_out bits
+  if (d_out < 1 || d_out > LF_MAX_DOUT || S < 0 || S * d_out > 32) return (int)hipErrorInvalidValue;
   if (meta.n_groups < 1 || meta.n_groups > LF_MAX_GROUPS || meta.n_terms > LF_MAX_TERMS ||
       meta.n_scal > LF_MAX_SCAL || blk0 < 0 || nblk < 1 || blk0 + nblk > n_blocks)
     return (int)hipErrorInvalidValue;
@@ -308,11 +321,11 @@ int tdq_loss_fused_range(const int* code, const float* consts, const void* outs,
 // do_reduce = 0: only the loss kernel (dJ, dlam, block partials); the fused step tail
 // (tdq_step_tail_bf3 / tdq_dp_tail_a_bf3) reduces the partials itself
 int tdq_loss_fused(const int* code, const float* consts, const void* outs, const void* groups,
-                   const void* ptrs, int n_groups, int n_terms, int n_scal, int S, int d_in, int N,
+                   const void* ptrs, int n_groups, int n_terms, int n_scal, int S, int d_in, int N, int d_out,
                    const float* J, const float* X, float* dJ, float* partials, int n_blocks, int max_regs,
                    float* losses, float* total, float* dscal, int with_total, int do_reduce, void* stream) {
-  int rc = tdq_loss_fused_range(code, consts, outs, groups, ptrs, n_groups, n_terms, n_scal, S, d_in, N, J, X, dJ,
-                                partials, n_blocks, 0, n_blocks, max_regs, stream);
+  int rc = tdq_loss_fused_range(code, consts, outs, groups, ptrs, n_groups, n_terms, n_scal, S, d_in, N, d_out, J, X,
+                                dJ, partials, n_blocks, 0, n_blocks, max_regs, stream);
   if (rc || !do_reduce) return rc;
   return loss_reduce(partials, n_blocks, n_terms, n_scal, losses, total, dscal, with_total, stream);
 }

@@ -23,9 +23,14 @@ of the group, zeros included), ``dlam`` per point and block partials of losses /
 gradients, then a deterministic reduction kernel finishes the sums.  :func:`run_reference`
 executes the same bytecode with torch (CPU tests / oracle).
 
+Networks with several outputs (``d_out <= 4``): a stream node carries its output column, the value
+``u_model`` returns is a :class:`SymCols` (columns of a stream) from which the callable picks
+components with the selections :mod:`.autodiff` supports, and a STREAM instruction's last operand
+is ``stream | column << 8`` (the plain stream index for one output).
+
 Anything the tracer cannot express (non-elementwise ops, data-dependent Python control flow on
-values, multi-output networks) makes :func:`build` return ``None`` and the solver keeps the
-autograd-composed loss.
+values, arithmetic on a multi-column stream, more than 4 outputs) makes :func:`build` return
+``None`` and the solver keeps the autograd-composed loss.
 """
 from __future__ import annotations
 
@@ -44,6 +49,8 @@ OP = dict(STREAM=1, COORD=2, VAL=3, CONST=4, LAM=5, SCAL=6,
 UNARY = {"neg": "NEG", "sin": "SIN", "cos": "COS", "exp": "EXP", "tanh": "TANH", "log": "LOG",
          "sqrt": "SQRT", "square": "SQUARE"}
 MAX_REGS = 120
+MAX_D_OUT = 4          # the fused jet kernels' limit; wider heads run on the layered engine, unfused
+COL_SHIFT = 8          # STREAM operand = stream index | output column << COL_SHIFT
 
 
 class TraceError(RuntimeError):
@@ -217,18 +224,80 @@ class _OnesMarker:
     ``torch.autograd.grad`` as the cotangent, see :func:`autodiff._routed_autograd_grad`)."""
 
 
+class SymCols:
+    """Output columns ``[lo, hi)`` of derivative stream ``mi`` of a network with several outputs:
+    what ``u_model(...)`` returns while tracing.  It only supports the column selections of
+    :mod:`.autodiff` (one column gives a :class:`Sym`) and ``tdq.grad`` (the sum of the component
+    streams); anything else is a :class:`TraceError`, so the program is not fused."""
+
+    def __init__(self, ctx, mi, lo, hi):
+        self.ctx, self.mi, self.lo, self.hi = ctx, mi, lo, hi
+        ctx.register(self, mi, False, (lo, hi))
+
+    def _pick(self, a, b):
+        if b - a == 1:
+            return self.ctx.stream(self.mi, a)
+        return SymCols(self.ctx, self.mi, a, b)
+
+    def __getitem__(self, idx):
+        cols = autodiff._col_index(idx, self.lo, self.hi)
+        if cols is None:
+            raise TraceError(f"unsupported index {idx!r} of a multi-column stream in a traced expression")
+        return self._pick(*cols)
+
+    @staticmethod
+    def _dim(dim):
+        if type(dim) is not int or dim not in (1, -1):
+            raise TraceError("split / unbind of a multi-column stream along a dimension other than 1")
+
+    def split(self, size, dim=0):
+        self._dim(dim)
+        if type(size) is not int or size < 1:
+            raise TraceError("split of a multi-column stream with other than one integer size")
+        return tuple(self._pick(a, min(a + size, self.hi)) for a in range(self.lo, self.hi, size))
+
+    def unbind(self, dim=0):
+        self._dim(dim)
+        return tuple(self._pick(a, a + 1) for a in range(self.lo, self.hi))
+
+    def __getattr__(self, name):
+        raise TraceError(f"unsupported tensor method .{name}() of a multi-column stream in a traced expression")
+
+    @property
+    def shape(self):
+        return (1, self.hi - self.lo)
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        name = getattr(func, "__name__", str(func))
+        if name in ("split", "unbind") and args and isinstance(args[0], SymCols):
+            return getattr(args[0], name)(*args[1:], **(kwargs or {}))
+        if name in ("cat", "stack", "hstack", "concat"):
+            return _CatMarker()
+        if name == "ones_like":
+            return _OnesMarker()
+        raise TraceError(f"unsupported torch function {name} of a multi-column stream")
+
+
 class _TraceCtx(autodiff._Ctx):
     """tdq.grad / u_model resolution while tracing (mirrors :class:`autodiff.JetContext`)."""
 
-    def __init__(self, g, seg, coords):
+    def __init__(self, g, seg, coords, d_out=1):
         super().__init__(coords)
-        self.g, self.seg = g, seg
+        self.g, self.seg, self.d_out = g, seg, d_out
+
+    def stream(self, mi, col=0):
+        """The registered Sym of stream ``mi`` of output column ``col``."""
+        key = ("stream", self.seg, mi) if self.d_out == 1 else ("stream", self.seg, mi, col)
+        s = Sym(self.g, self.g.add(key))
+        self.register(s, mi, False, (col, col + 1))
+        return s
 
     def proxy(self):
         def u_model(*args, **kw):
-            s = Sym(self.g, self.g.add(("stream", self.seg, ())))
-            self.register(s, (), False)
-            return s
+            if self.d_out > 1:
+                return SymCols(self, (), 0, self.d_out)
+            return self.stream(())
         return u_model
 
     def grad(self, y, x):
@@ -237,15 +306,19 @@ class _TraceCtx(autodiff._Ctx):
         if info is None or var is None:
             raise TraceError("grad() of a tensor that is not a derivative stream of u_model")
         mi = tuple(sorted(info[0] + (var,)))
-        s = Sym(self.g, self.g.add(("stream", self.seg, mi)))
-        self.register(s, mi, False)
+        lo, hi = info[2]
+        s = self.stream(mi, lo)
+        if hi - lo > 1:    # tf.gradients semantics: the sum over the columns
+            for q in range(lo + 1, hi):
+                s = s + self.stream(mi, q)
+            self.register(s, mi, True, (lo, hi))
         return s
 
 
-def trace_callable(g, fn, seg, d_in, extra=()):
+def trace_callable(g, fn, seg, d_in, extra=(), d_out=1):
     """Trace ``fn(u_model, *extra, *coords)`` for segment slot ``seg``; returns list of Sym outputs."""
     coords = [Sym(g, g.add(("coord", seg, j))) for j in range(d_in)]
-    ctx = _TraceCtx(g, seg, coords)
+    ctx = _TraceCtx(g, seg, coords, d_out)
     with autodiff.use(ctx):
         out = fn(ctx.proxy(), *extra, *coords)
     outs = list(out) if isinstance(out, (tuple, list)) else [out]
@@ -255,6 +328,8 @@ def trace_callable(g, fn, seg, d_in, extra=()):
             res.append(o)
         elif isinstance(o, (list, tuple)) and len(o) == 1 and isinstance(o[0], Sym):
             res.append(o[0])
+        elif isinstance(o, SymCols):
+            raise TraceError("a callable returns a multi-column stream")
         else:
             # a constant output (e.g. u_x of a linear net) is a valid, constant residual
             res.append(Sym(g, g.add(("const", float(torch.as_tensor(o).reshape(-1)[0])))))
@@ -269,6 +344,7 @@ class Program:
         self.consts = []
         self.outputs = []     # (f_reg, w_reg, term_id, c)
         self.stream_regs = {}  # (seg_slot, stream_index) -> reg
+        self.stream_cols = {}  # (seg_slot, stream_index, output column) -> reg
         self.n_regs = 0
 
 
@@ -297,11 +373,12 @@ def compile_graph(g, outputs, stream_index, n_streams, val_ids, lam_ids, scal_id
         reg[i] = r
         kind = k[0]
         if kind == "stream":
-            _, seg, mi = k
+            seg, mi, col = k[1], k[2], (k[3] if len(k) > 3 else 0)
             if mi not in stream_index:
                 raise TraceError(f"stream {mi} not in the jet plan")
-            P.code.append([OP["STREAM"], r, seg, stream_index[mi]])
+            P.code.append([OP["STREAM"], r, seg, stream_index[mi] | (col << COL_SHIFT)])
             P.stream_regs[(seg, stream_index[mi])] = r
+            P.stream_cols[(seg, stream_index[mi], col)] = r
         elif kind == "coord":
             P.code.append([OP["COORD"], r, k[1], k[2]])
         elif kind == "val":
@@ -349,6 +426,7 @@ class FusedLoss:
         self.scal_slots = []      # ("lam", index) or ("extra", k) per scalar id
         self.lam_offsets = {}     # lambda index -> (lo, hi) slice read by a minibatch program
         self.n_streams = 0
+        self.d_out = 1            # network outputs: J and dJ are (n_streams, N, d_out)
 
 
 def _weight(g, lam_sym, kind_g, gfun):
@@ -370,7 +448,12 @@ def build(prog, lambdas, extras_example=None):
     Returns ``None`` if any term cannot be fused (the caller keeps the autograd loss)."""
     if prog.plan is None or prog.backend not in ("hip", "jet"):
         return None
-    if prog.net.layer_sizes[-1] != 1:
+    d_out = prog.net.layer_sizes[-1]
+    if d_out > MAX_D_OUT:
+        prog.reasons.append(f"loss fusion disabled: {d_out} network outputs (the fused loss takes up to {MAX_D_OUT})")
+        return None
+    if d_out > 1 and prog.mixed:
+        prog.reasons.append("loss fusion disabled: high-order segments of a network with several outputs")
         return None
     try:
         return _build(prog, lambdas)
@@ -381,8 +464,11 @@ def build(prog, lambdas, extras_example=None):
 
 def _build(prog, lambdas):
     fl = FusedLoss()
+    d_out = fl.d_out = prog.net.layer_sizes[-1]
     # mixed programs: the main plan's rows, then the high-order rows (LossProgram.fused_streams)
     stream_index, fl.n_streams = prog.fused_streams()
+    if d_out > 1 and fl.n_streams * d_out > 32:   # the kernels' per-group mask of the (stream, output) pairs read
+        raise TraceError(f"{fl.n_streams} streams x {d_out} outputs (the fused loss takes 32 pairs)")
     g_by_seg = {}
     gs = []
     lam_id = {}
@@ -433,6 +519,9 @@ def _build(prog, lambdas):
         fl.val_arrays.append(v.reshape(-1).to(torch.float32).contiguous())
         return Sym(g, g.add(("val", vid)))
 
+    def trace(g, fn, slot, extra=()):
+        return trace_callable(g, fn, slot, prog.d_in, extra, d_out)
+
     osum = "outside" if prog.weight_outside_sum else "inside"
     for ti, t in enumerate(prog.terms):
         fl.term_names.append(t.name)
@@ -441,11 +530,27 @@ def _build(prog, lambdas):
             gr, g = group_for([t.seg])
             slot = gr.segs.index(t.seg)
             n = prog.segments[t.seg].n
-            u = Sym(g, g.add(("stream", slot, ())))
-            f = u - val_sym(g, t, t.val, n)
+            if d_out == 1:
+                u = Sym(g, g.add(("stream", slot, ())))
+                f = u - val_sym(g, t, t.val, n)
+                w = _weight(g, lam_sym(g, t), osum, None)
+                c = c_base / (t.denom if t.denom is not None else n)
+                gr.outputs.append((f.i, w.i, ti, c))
+                continue
+            # one output per selected column: the term is the mean over the n * n_cols elements of
+            # (w (u_q - val_q))^2, column q of a (n, n_cols) target going with the q-th selected output
+            cols = list(range(d_out)) if getattr(t, "cols", None) is None else list(t.cols)
+            val = t.val if torch.is_tensor(t.val) else torch.as_tensor(t.val, dtype=torch.float32)
+            per_col = val.dim() == 2 and val.shape[1] > 1
+            if per_col and val.shape[1] != len(cols):
+                raise TraceError(f"{t.name}: {val.shape[1]} target columns for {len(cols)} outputs")
             w = _weight(g, lam_sym(g, t), osum, None)
-            c = c_base / (t.denom if t.denom is not None else n)
-            gr.outputs.append((f.i, w.i, ti, c))
+            c = c_base / (t.denom if t.denom is not None else n * len(cols))
+            v = None if per_col else val_sym(g, t, val, n)
+            for k, q in enumerate(cols):
+                u = Sym(g, g.add(("stream", slot, (), q)))
+                f = u - (val_sym(g, t, val[:, k], n) if per_col else v)
+                gr.outputs.append((f.i, w.i, ti, c))
         elif t.kind == "residual":
             gr, g = group_for([t.seg])
             slot = gr.segs.index(t.seg)
@@ -453,7 +558,7 @@ def _build(prog, lambdas):
             key = ("res", id(t.fn), t.seg)
             if key not in g_by_seg:
                 extra = tuple(_extra_syms(g, t.extra, scal_id, fl))
-                g_by_seg[key] = trace_callable(g, t.fn, slot, prog.d_in, extra)
+                g_by_seg[key] = trace(g, t.fn, slot, extra)
             f = g_by_seg[key][t.index]
             ls = lam_sym(g, t)
             gfun = prog.g if (ls is not None and prog.g is not None) else None
@@ -466,8 +571,8 @@ def _build(prog, lambdas):
                 n = prog.segments[su].n
                 ou, ol = [], []
                 for fn in t.fns:
-                    ou += trace_callable(g, fn, gr.segs.index(su), prog.d_in)
-                    ol += trace_callable(g, fn, gr.segs.index(sl), prog.d_in)
+                    ou += trace(g, fn, gr.segs.index(su))
+                    ol += trace(g, fn, gr.segs.index(sl))
                     if prog.periodic_legacy:
                         break
                 if prog.periodic_legacy:
@@ -482,7 +587,7 @@ def _build(prog, lambdas):
                 n = prog.segments[si].n
                 v = val_sym(g, t, t.val, n)
                 for fn in t.fns:
-                    for o in trace_callable(g, fn, gr.segs.index(si), prog.d_in):
+                    for o in trace(g, fn, gr.segs.index(si)):
                         f = v - o
                         w = _weight(g, lam_sym(g, t), osum, None)
                         gr.outputs.append((f.i, w.i, ti, c_base / n))
@@ -591,7 +696,7 @@ def run_reference(fl, prog, J, lambdas, scalars):
         for op, dst, a, b in P.code:
             if op == OP["STREAM"]:
                 s = prog.segments[gr.segs[a]]
-                v = J[b, s.offset:s.offset + n, 0]
+                v = J[b & ((1 << COL_SHIFT) - 1), s.offset:s.offset + n, b >> COL_SHIFT]
             elif op == OP["COORD"]:
                 s = prog.segments[gr.segs[a]]
                 v = prog.X_all[s.offset:s.offset + n, b]

@@ -171,6 +171,32 @@ class CollocationSolverND:
         self._engine = None
         self._lbfgs_engine = None
         self._state = None
+        for i, bc in enumerate(self.bcs):   # a target that does not fit the outputs is refused here
+            if bc.isInit or bc.isDirichlect:
+                self._value_target(f"BC_{i} ({type(bc).__name__})", bc.val, getattr(bc, "outputs", None))
+
+    def _value_target(self, name, val, outputs=None):
+        """``(target, output columns or None)`` of a value condition (Dirichlet / IC / data) on a
+        network with ``d_out`` outputs: a scalar or one column ``(n, 1)`` is the target of every
+        selected output, ``k`` columns are the targets of the ``k`` selected outputs (all ``d_out``
+        without ``outputs=``), in order.  Anything else is a ``ValueError`` naming the condition."""
+        d_out = int(self.layer_sizes[-1])
+        cols = None if outputs is None else list(outputs)
+        if cols is not None and any(c >= d_out for c in cols):
+            raise ValueError(f"{name}: outputs={cols} on a network with {d_out} output(s)")
+        n_sel = d_out if cols is None else len(cols)
+        val = torch.as_tensor(np.asarray(val) if not torch.is_tensor(val) else val.detach().cpu(),
+                              dtype=torch.float32, device=self.device)
+        if val.numel() == 1:
+            return val.reshape(()), cols
+        if val.dim() < 2 or val.shape[1] == 1:
+            val = val.reshape(-1, 1)
+        if val.dim() != 2 or val.shape[1] not in (1, n_sel):
+            k = val.shape[1] if val.dim() == 2 else tuple(val.shape)
+            raise ValueError(f"{name}: {k} target functions / columns for {n_sel} network output(s)"
+                             + (f" (outputs={cols})" if cols is not None else "")
+                             + f"; give one (applied to every output) or {n_sel}")
+        return val.contiguous(), cols
 
     def _init_lambdas(self, init_weights, dict_adaptive):
         ctx = self.dist_ctx
@@ -208,8 +234,19 @@ class CollocationSolverND:
             raise Exception("Assimilate needs to be set to 'true' for data assimilation. Re-initialize "
                             "CollocationSolverND with assimilate=True.")
         self.data_x, self.data_t, self.data_s = x, t, y
+        if hasattr(self, "layer_sizes"):
+            self._data_target()
         self._programs = {}
         self._engine = None
+
+    def _data_target(self):
+        """Assimilation targets: ``(n, 1)``, or one column per output ``(n, d_out)``."""
+        y = np.asarray(self.data_s)
+        n = np.asarray(self.data_x).size
+        y = y.reshape(n, -1) if y.ndim > 1 and y.shape[0] == n else y.reshape(-1, 1)
+        if y.shape[0] != n:
+            raise ValueError(f"compile_data: {y.shape[0]} target rows for {n} data points")
+        return self._value_target("compile_data", y)[0]
 
     # ================================================================== program =========
     def _adaptive_flags(self, key):
@@ -262,20 +299,16 @@ class CollocationSolverND:
                                    lam=lam, scale=rep_scale))
             elif bc.isInit or bc.isDirichlect:
                 s = prog.add_segment(name, bc.input)
-                val = bc.val
-                val = torch.as_tensor(np.asarray(val) if not torch.is_tensor(val) else val.detach().cpu(),
-                                      dtype=torch.float32, device=self.device)
-                val = val.reshape(-1, 1) if val.numel() > 1 else val.reshape(())
+                val, cols = self._value_target(f"{name} ({type(bc).__name__})", bc.val, getattr(bc, "outputs", None))
                 prog.add_term(Term(name, "ic" if bc.isInit else "dirichlet", seg=s, val=val, lam=lam,
-                                   scale=rep_scale))
+                                   scale=rep_scale, cols=cols))
             else:
                 raise Exception("Boundary condition type is not acceptable")
         if self.assimilate and self.data_s is not None:
             Xd = np.hstack([np.reshape(np.asarray(self.data_x), (-1, 1)),
                             np.reshape(np.asarray(self.data_t), (-1, 1))])
             s = prog.add_segment("data", Xd)
-            val = torch.as_tensor(np.reshape(np.asarray(self.data_s), (-1, 1)), dtype=torch.float32,
-                                  device=self.device)
+            val = self._data_target()
             prog.add_term(Term("Data", "data", seg=s, val=val, scale=rep_scale))
         Xr = self.X_f_local
         n_glob = self.N_f

@@ -69,6 +69,7 @@ class Term:
         self.kind = kind
         self.lam = None          # index into the lambda list or None
         self.scale = 1.0         # 1/world for replicated terms
+        self.cols = None         # value terms: the output columns they apply to (None: all)
         self.denom = None        # global denominator override for sharded means
         self.__dict__.update(kw)
 
@@ -351,6 +352,8 @@ class LossProgram:
         osum = self.weight_outside_sum
         if t.kind in ("dirichlet", "ic", "data"):
             u = self.u_on(t.seg, J)
+            if t.cols is not None:
+                u = u[:, t.cols]
             val = t.val
             if lam is not None:
                 return MSE(u, val, lam, osum, denom=t.denom)

@@ -76,8 +76,8 @@ def _declare(lib):
         "tdq_adam_multi": (I, [P, I, P, P, P]),
         "tdq_step_book": (I, [P, P, I, I, P, L, P, P, P, P, P, I, P]),
         "tdq_best_track": (I, [P, P, P, P, P, P, L, P]),
-        "tdq_loss_fused": (I, [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, P, P, I, I, P]),
-        "tdq_loss_fused_range": (I, [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, I, I, I, I, P]),
+        "tdq_loss_fused": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, I, I, P, P, P, I, I, P]),
+        "tdq_loss_fused_range": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, I, I, I, I, P]),
         "tdq_loss_meta_sizes": (I, [P]),
         "tdq_loss_reduce_partials": (I, [P, I, I, I, P, P, P, I, P]),
         "tdq_lbfgs_nst": (I, []),

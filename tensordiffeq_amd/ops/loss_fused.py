@@ -27,6 +27,11 @@ class FusedLossOp:
                 or len(fl.scal_slots) > MAX_SCAL or len(fl.term_names) > MAX_TERMS:
             raise ValueError("fused loss program exceeds kernel table limits")
         self.fl, self.prog = fl, prog
+        # J / dJ are (rows, N, d_out); the groups' ``loaded`` masks hold one bit per (stream, output)
+        self.d_out = d_out = int(getattr(fl, "d_out", 1))
+        if d_out > 1 and fl.n_streams * d_out > 32:
+            raise ValueError(f"fused loss: {fl.n_streams} streams x {d_out} outputs exceed the kernel's 32 "
+                             "(stream, output) slots")
         code, consts, outs, groups = [], [], [], []
         self.group_meta = []   # (block_off, phase, n, seg_off, n_slots, loaded) per group (ops/loss_jit.py)
         spans = []
@@ -37,8 +42,9 @@ class FusedLossOp:
             if len(gr.segs) > MAX_SLOTS:
                 raise ValueError("group reads more than 2 segments")
             loaded = [0] * MAX_SLOTS
-            for (slot, s) in P.stream_regs:
-                loaded[slot] |= 1 << s
+            for (slot, s, q) in P.stream_cols:
+                loaded[slot] |= 1 << (s * d_out + q)
+            loaded = [v - (1 << 32) if v >= 1 << 31 else v for v in loaded]   # as int32 bit patterns
             offs = [prog.segments[s].offset for s in gr.segs]
             seg_off = offs + [0] * (MAX_SLOTS - len(gr.segs))
             # single-segment groups: block boundaries on absolute multiples of LF_BLOCK (LFGroup.phase)
@@ -99,7 +105,7 @@ class FusedLossOp:
         self.ptrs = torch.from_numpy(ptrs[:MAX_VAL + 2 * MAX_LAM + MAX_SCAL].copy()).to(dev)
         N = prog.X_all.shape[0]
         self.N = N
-        self.dJ = torch.zeros((fl.n_streams, N, 1), device=dev)
+        self.dJ = torch.zeros((fl.n_streams, N, d_out), device=dev)
         self.partials = torch.zeros(self.n_blocks * (self.n_terms + self.n_scal), device=dev)
         self.losses = torch.zeros(self.n_terms, device=dev)
         self.total = torch.zeros((), device=dev)
@@ -119,6 +125,7 @@ class FusedLossOp:
         per-term losses and scalar gradients are reduced by the fused step tail
         (``jet_hip.step_tail`` / ``jet_hip.dp_tail_a``)."""
         lib = _lib.load()
+        self._check_J(J)
         if self.jit is not None:
             st = _lib.stream_ptr(J.device)
             self.jit.launch(J, self.prog.X_all, self.dJ, self.partials, self.ptrs, 0, self.n_blocks, st)
@@ -130,13 +137,21 @@ class FusedLossOp:
             return self.total, self.losses, self.dJ, self.dlam, self.dscal
         rc = lib.tdq_loss_fused(_lib.ptr(self.code), _lib.ptr(self.consts), _lib.ptr(self.outs),
                                 _lib.ptr(self.groups), _lib.ptr(self.ptrs), self.n_groups, self.n_terms,
-                                self.n_scal, self.fl.n_streams, self.prog.d_in, self.N, _lib.ptr(J),
+                                self.n_scal, self.fl.n_streams, self.prog.d_in, self.N, self.d_out, _lib.ptr(J),
                                 _lib.ptr(self.prog.X_all), _lib.ptr(self.dJ), _lib.ptr(self.partials),
                                 self.n_blocks, self.max_regs, _lib.ptr(self.losses), _lib.ptr(self.total),
                                 _lib.ptr(self.dscal), int(bool(with_total)), int(bool(reduce)),
                                 _lib.stream_ptr(J.device))
         _lib.check(rc, "tdq_loss_fused")
         return self.total, self.losses, self.dJ, self.dlam, self.dscal
+
+    def _check_J(self, J):
+        """Several outputs: the kernels index ``J`` as ``(rows, N, d_out)`` and the specialised one
+        reads a point's outputs with one 8- / 16-byte access."""
+        if self.d_out > 1 and (tuple(J.shape[1:]) != (self.N, self.d_out) or J.shape[0] < self.fl.n_streams
+                               or not J.is_contiguous() or J.data_ptr() % 16 or J.dtype != torch.float32):
+            raise ValueError(f"fused loss: J must be a contiguous, 16-byte aligned float32 (>= {self.fl.n_streams}, "
+                             f"{self.N}, {self.d_out}) tensor, got {tuple(J.shape)}")
 
     def split_block(self, a):
         """Block index ``b`` such that blocks ``[0, b)`` touch only points ``< a`` and blocks
@@ -155,13 +170,14 @@ class FusedLossOp:
         """Blocks ``[blk0, blk0 + nblk)`` only (dJ / dlam / block partials of their points; the
         fused step tail reduces the partials), on the current stream."""
         lib = _lib.load()
+        self._check_J(J)
         if self.jit is not None:
             self.jit.launch(J, self.prog.X_all, self.dJ, self.partials, self.ptrs, blk0, nblk,
                             _lib.stream_ptr(J.device))
             return
         rc = lib.tdq_loss_fused_range(_lib.ptr(self.code), _lib.ptr(self.consts), _lib.ptr(self.outs),
                                       _lib.ptr(self.groups), _lib.ptr(self.ptrs), self.n_groups, self.n_terms,
-                                      self.n_scal, self.fl.n_streams, self.prog.d_in, self.N, _lib.ptr(J),
+                                      self.n_scal, self.fl.n_streams, self.prog.d_in, self.N, self.d_out, _lib.ptr(J),
                                       _lib.ptr(self.prog.X_all), _lib.ptr(self.dJ), _lib.ptr(self.partials),
                                       self.n_blocks, int(blk0), int(nblk), self.max_regs,
                                       _lib.stream_ptr(J.device))
