@@ -4,7 +4,8 @@ i h_t + 1/2 h_xx + |h|^2 h = 0 with h = u + i v on x in [-5, 5], t in [0, pi/2]:
     -v_t + 1/2 u_xx + (u^2 + v^2) u = 0,     u_t + 1/2 v_xx + (u^2 + v^2) v = 0,
 h(x, 0) = sech x (u = sech x, v = 0), periodic in x for u, v, u_x, v_x.  The exact solution is the
 soliton u = sech x cos(t/2), v = sech x sin(t/2); the relative L2 error of |h| against it is printed,
-so the example needs no data file.  Net [2, 100 x 4, 2], N_f = 20,000, Adam 10k + L-BFGS 10k.
+so the example needs no data file.  Net [2, 100 x 4, 2], N_f = 20,000, Adam 10k + L-BFGS 10k
+(``--width 128`` is the width the one-launch step serves; the route is printed).
 The components are picked from the network output with ``h[:, 0:1]`` / ``h[:, 1:2]``; the program
 runs on the jet kernels (``backend == "hip"`` on a GPU) with the fused loss.
 Run:  python examples/schrodinger.py [--iters 10000 --newton 10000]
@@ -60,12 +61,15 @@ def build(args):
     init = IC(Domain, [ic_u, ic_v], var=[["x"], ["x"]])       # one target function per output
     x_periodic = periodicBC(Domain, ["x"], [deriv_model])
     model = tdq.CollocationSolverND(verbose=not args.quiet)
-    model.compile([2, 100, 100, 100, 100, 2], f_model, Domain, [init, x_periodic], **solver_kw(args))
+    width = int(getattr(args, "width", 100))
+    model.compile([2, width, width, width, width, 2], f_model, Domain, [init, x_periodic], **solver_kw(args))
     return model, Domain
 
 
 def main(argv=None):
-    args = parser(__doc__.splitlines()[0], iters=10000, newton=10000).parse_args(argv)
+    ap = parser(__doc__.splitlines()[0], iters=10000, newton=10000)
+    ap.add_argument("--width", type=int, default=100, help="hidden width (128: the one-launch step's)")
+    args = ap.parse_args(argv)
     model, Domain = build(args)
     backend = model.active_backend
     if model.device.type == "cuda" and args.backend == "auto":
@@ -84,7 +88,9 @@ def main(argv=None):
     err = float(tdq.find_L2_error(np.hypot(h_pred[:, 0:1], h_pred[:, 1:2]), np.hypot(u, v)[:, None]))
     res = report("schrodinger", {"l2_error_abs_h": err, "loss": float(model.losses[-1]["Total Loss"]),
                                  "adam_s": t1 - t0, "lbfgs_s": t2 - t1, "backend": backend,
-                                 "fused_loss": model.program().fused_op is not None}, args.quiet, model=model)
+                                 "fused_loss": model.program().fused_op is not None,
+                                 "fused_step_reason": str(getattr(model.program(), "fused_step_reason", "not requested"))},
+                 args.quiet, model=model)
     return res
 
 

@@ -59,12 +59,13 @@ __host__ __device__ constexpr int fz_img_elems(int WT, int S, int LM) {
 //   aux copy (the aux image of jet_bf3.h with n_hidden = LM + 1: K0 rows, b0, hidden biases at bh,
 //   Ko [W][4] at ko, bo at bo; rounded up to 4 floats) | xs [PT][TDQ_MAXD] | ubs [S][PT][4] dJ of the
 //   tile | part: NQ sets (one per 16-point column tile) of pq partials - biases of layers 0..LM
-//   [LM + 1][W], K0 [d_in][W], Ko [W][4] - and 4 spare floats | outp [NW waves][S][PT] output-layer
-//   partial dots | lpre [PT] the loss's prefetched per-point input
+//   [LM + 1][W], K0 [d_in][W], Ko [W][4] - and 4 spare floats | outp [NW waves][S][PT][DO] output-layer
+//   partial dots (the DO network outputs of one (stream, point) side by side) | lpre [PT] the loss's
+//   prefetched per-point input
 struct FzFl {
   int bh, ko, bo, xs, ubs, part, pq, outp, lpre, total;
 };
-__host__ __device__ constexpr FzFl fz_fl(int W, int d_in, int S, int LM, int PT, int NQ, int NW) {
+__host__ __device__ constexpr FzFl fz_fl(int W, int d_in, int S, int LM, int PT, int NQ, int NW, int DO = 1) {
   FzFl f{};
   f.bh = (d_in + 1) * W;
   f.ko = (d_in + LM + 1) * W;
@@ -74,12 +75,12 @@ __host__ __device__ constexpr FzFl fz_fl(int W, int d_in, int S, int LM, int PT,
   f.part = f.ubs + S * PT * 4;
   f.pq = (LM + 1) * W + d_in * W + 4 * W;
   f.outp = f.part + NQ * f.pq + 4;
-  f.lpre = f.outp + NW * S * PT;
+  f.lpre = f.outp + NW * S * PT * DO;
   f.total = f.lpre + PT;
   return f;
 }
 __host__ __device__ inline int fz_lds_bytes(const NetDims& d, int WT, int S, int LM) {
-  return fz_img_elems(WT, S, LM) * 2 + fz_fl(16 * WT, d.d_in, S, LM, FZ_PT, 2, 4).total * 4;
+  return fz_img_elems(WT, S, LM) * 2 + fz_fl(16 * WT, d.d_in, S, LM, FZ_PT, 2, 4, d.d_out).total * 4;
 }
 
 // Layer 0 (input -> width, VALU) of feature tile t at one point x (LDS row) - computed twice per
@@ -336,6 +337,26 @@ __device__ __forceinline__ float fz_jsum(const float* jv, int s, int k, float bo
   for (int w = 1; w < NW; ++w) a += jv[(w * S + s) * PT + k];
   return s == 0 ? a + bo : a;
 }
+// The same for a network with DOUT > 1 outputs: J of (stream s, point k, output q) from
+// jv[((w * S + s) * PT + k) * DOUT + q] - the outputs of one (stream, point) in one 8- / 16-byte LDS
+// read for 2 / 4 outputs (the q of one (s, k) share it).  NW = 1 (the bf16x3 objective): the J-sum
+// phase has summed the waves and added the biases, bo is not read.
+template <int S, int PT, int NW, int DOUT>
+__device__ __forceinline__ float fz_jsum_q(const float* jv, int s, int k, int q, const float* bo) {
+  static_assert(DOUT >= 2 && DOUT <= 4, "fz_jsum_q: 2-4 outputs");
+  float a = 0.f;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    const float* e = jv + ((w * S + s) * PT + k) * DOUT;
+    float v;
+    if constexpr (DOUT == 2) v = (*reinterpret_cast<const f32x2*>(e))[q];
+    else if constexpr (DOUT == 4) v = (*reinterpret_cast<const f32x4*>(e))[q];
+    else v = e[q];
+    a = w == 0 ? v : a + v;
+  }
+  if constexpr (NW > 1) return s == 0 ? a + bo[q] : a;
+  return a;
+}
 
 // ---- Steps of the tile loop that fz_body below (32-point tiles) and fz3_body of jet_fused3.h
 // (16-point tiles) share, beside FzFl, fz_h0, fz_tr and fz_jsum above.  The other steps the two
@@ -375,11 +396,13 @@ __device__ __forceinline__ void fz_setup(const FzParams& P, float* aux, int tid)
 }
 
 // The generated loss (ops/fused_step.py gen_loss) has this interface:
-//   NACC: loss / scalar-gradient sums per point-thread;
+//   NACC: loss / scalar-gradient sums per point-thread; DOUT: the network's outputs (1-4);
 //   eval<S, PT, NW>(jv, xs, t, n, N, ptrs, ubs, acc, pv, bo) on the tile's point-thread t (point n
 //   of the fused point set): J of the tile's point k, stream s = fz_jsum(jv, s, k, bo), coordinates at
 //   xs[k * TDQ_MAXD + j]; writes dJ of the points it owns to ubs[(s * PT + k) * 4] (zero for points
-//   outside every loss group) and adds loss / scalar-gradient sums to acc;
+//   outside every loss group) and adds loss / scalar-gradient sums to acc; with DOUT > 1 outputs J of
+//   output q = fz_jsum_q(jv, s, k, q, bo) (bo: the bias array), and dJ of EVERY output q < DOUT of every
+//   (stream, point) goes to ubs[(s * PT + k) * 4 + q] - zero where the program reads nothing;
 //   pre(n, N, ptrs): the first per-point global input of point n's group (an SA weight or a data
 //   value), which the kernel loads one tile ahead (with the coordinates) and passes in as pv - the
 //   loss phase then waits for no global load on the common groups.
@@ -393,7 +416,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   // the stream spec and input width as compile-time constants of the generated loss struct
   // (ops/fused_step.py spec_source): the one-hot stream selects and first-layer loops fold away
   constexpr JetSpec sp = LossF::SPEC;
-  constexpr int DIN = LossF::DIN;
+  constexpr int DIN = LossF::DIN, DOUT = LossF::DOUT;
   constexpr int W = 16 * WT, OPW = WT / 4, RS = bf3_img_rs(WT), SIMG = FZ_PT * RS, PT = FZ_PT;
   constexpr int NR = WT / 4, NC = WT / 2;  // dK tiles per wave: row block (w >> 1), column block (w & 1)
   constexpr int ZS = 0;                    // slot of h_LM / zb_LM (h_0's slot once layer 1 has read it)
@@ -404,7 +427,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   // compile-time aux-image / LDS offsets (d_in = DIN, n_hidden = LM + 1): LDS accesses then take
   // immediate offsets instead of runtime address arithmetic.  Two partial sets (one per column
   // tile), output dots of the 4 waves of a column tile
-  constexpr FzFl F = fz_fl(W, DIN, S, LM, PT, 2, 4);
+  constexpr FzFl F = fz_fl(W, DIN, S, LM, PT, 2, 4, DOUT);
   float* aux = reinterpret_cast<float*>(img + fz_img_elems(WT, S, LM));
   float *xs = aux + F.xs, *ubs = aux + F.ubs, *part = aux + F.part, *outp = aux + F.outp, *lpre = aux + F.lpre;
 
@@ -444,7 +467,10 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   fz_setup<WT, LM, F.xs>(P, aux, tid);
   f32x4 dk[LM][NR][NC];
   float lacc[LossF::NACC];  // this point-thread's loss / scalar-gradient sums (all tiles)
-  float bo_acc = 0.f;       // this point-thread's output-bias gradient (its points' value-stream dJ)
+  float bo_acc = 0.f;  // this point-thread's output-bias gradient (its points' value-stream dJ)
+  float bo_q[DOUT];    // ... of outputs 1.. of a network with several (bo_acc: output 0)
+#pragma unroll
+  for (int qo = 0; qo < DOUT; ++qo) bo_q[qo] = 0.f;
 #pragma unroll
   for (int k = 0; k < LossF::NACC; ++k) lacc[k] = 0.f;
 #pragma unroll
@@ -515,13 +541,31 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
       if (ly == LM) {  // output-layer partial dots of this wave's features -> LDS
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-          float a = 0.f;
+          if constexpr (DOUT == 1) {
+            float a = 0.f;
 #pragma unroll
-          for (int oo = 0; oo < OPW; ++oo)
+            for (int oo = 0; oo < OPW; ++oo)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) a = fmaf(hq[oo][s][c], Ko[(16 * (o0 + oo) + 4 * g + c) * 4], a);
-          const float r = col4_sum(a);
-          if (g == 0) outp[(wo * S + s) * FZ_PT + row] = r;
+              for (int c = 0; c < 4; ++c) a = fmaf(hq[oo][s][c], Ko[(16 * (o0 + oo) + 4 * g + c) * 4], a);
+            const float r = col4_sum(a);
+            if (g == 0) outp[(wo * S + s) * FZ_PT + row] = r;
+          } else {  // one dot per (stream, output), the outputs of a (stream, point) side by side
+            float a[DOUT];
+#pragma unroll
+            for (int qo = 0; qo < DOUT; ++qo) a[qo] = 0.f;
+#pragma unroll
+            for (int oo = 0; oo < OPW; ++oo)
+#pragma unroll
+              for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int qo = 0; qo < DOUT; ++qo)
+                  a[qo] = fmaf(hq[oo][s][c], Ko[(16 * (o0 + oo) + 4 * g + c) * 4 + qo], a[qo]);
+#pragma unroll
+            for (int qo = 0; qo < DOUT; ++qo) {
+              const float r = col4_sum(a[qo]);
+              if (g == 0) outp[((wo * S + s) * FZ_PT + row) * DOUT + qo] = r;
+            }
+          }
         }
       }
       if (ly < LM) fz_pre_w<WT, OPW>(wf, Wimg, ly + 1, o0, l);
@@ -536,7 +580,11 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
     // fewer, 0.1383 -> 0.1376 ms, profiles/r6ag_jsum_ab.txt)
     int tl = tid;
     asm volatile("" : "+v"(tl));
-    if (tl < PT) LossF::template eval<S, PT, 4>(outp, xs, tl, pb + tl, N, *P.lptrs, ubs, lacc, lpre[tl], aux[F.bo]);
+    if constexpr (DOUT == 1) {
+      if (tl < PT) LossF::template eval<S, PT, 4>(outp, xs, tl, pb + tl, N, *P.lptrs, ubs, lacc, lpre[tl], aux[F.bo]);
+    } else {
+      if (tl < PT) LossF::template eval<S, PT, 4>(outp, xs, tl, pb + tl, N, *P.lptrs, ubs, lacc, lpre[tl], aux + F.bo);
+    }
     __syncthreads();
     FZ_TS(9);
     // dbo: each point-thread adds its point's value-stream dJ (one LDS read; a 32-step loop on
@@ -544,6 +592,12 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
     tl = tid;
     asm volatile("" : "+v"(tl));
     if (tl < PT) bo_acc += ubs[tl * 4];
+    if constexpr (DOUT > 1) {
+      if (tl < PT) {
+#pragma unroll
+        for (int qo = 1; qo < DOUT; ++qo) bo_q[qo] += ubs[tl * 4 + qo];
+      }
+    }
     // ---- reverse through the output layer: hb = Ko ub, dKo, the top tanh layer's adjoint ----
 #pragma unroll
     for (int oo = 0; oo < OPW; ++oo) {
@@ -551,18 +605,42 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
       __bf16* im = slot(ZS);
       f32x4 h[S], hb[S], zb[S];
       fz_get_h<WT, S>(im, L, q, to, h);
-      f32x4 kq, pp = zero4();
+      if constexpr (DOUT == 1) {
+        f32x4 kq, pp = zero4();
 #pragma unroll
-      for (int c = 0; c < 4; ++c) kq[c] = Ko[(16 * to + 4 * g + c) * 4];
+        for (int c = 0; c < 4; ++c) kq[c] = Ko[(16 * to + 4 * g + c) * 4];
 #pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const float ub = ubs[(s * FZ_PT + row) * 4];
-        hb[s] = kq * ub;
-        pp += h[s] * ub;
-      }
-      {
-        const float r = row16_sum4(pp);
-        if ((p & 3) == 0) accKo[(16 * to + 4 * g + (p >> 2)) * 4] += r;
+        for (int s = 0; s < S; ++s) {
+          const float ub = ubs[(s * FZ_PT + row) * 4];
+          hb[s] = kq * ub;
+          pp += h[s] * ub;
+        }
+        {
+          const float r = row16_sum4(pp);
+          if ((p & 3) == 0) accKo[(16 * to + 4 * g + (p >> 2)) * 4] += r;
+        }
+      } else {  // hb[s] = sum_q Ko[.][q] ub[s][q]; dKo[.][q] += sum_s h[s] ub[s][q]
+        f32x4 kq[DOUT], pp[DOUT];
+#pragma unroll
+        for (int qo = 0; qo < DOUT; ++qo) {
+          pp[qo] = zero4();
+#pragma unroll
+          for (int c = 0; c < 4; ++c) kq[qo][c] = Ko[(16 * to + 4 * g + c) * 4 + qo];
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+#pragma unroll
+          for (int qo = 0; qo < DOUT; ++qo) {
+            const float ub = ubs[(s * FZ_PT + row) * 4 + qo];
+            hb[s] = qo == 0 ? kq[0] * ub : hb[s] + kq[qo] * ub;
+            pp[qo] += h[s] * ub;
+          }
+        }
+#pragma unroll
+        for (int qo = 0; qo < DOUT; ++qo) {
+          const float r = row16_sum4(pp[qo]);
+          if ((p & 3) == 0) accKo[(16 * to + 4 * g + (p >> 2)) * 4 + qo] += r;
+        }
       }
       tanh_jet_b<S, NSO>(sp, h, hb, zb);
       const float r = row16_sum4(zb[0]);
@@ -700,10 +778,17 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
       gs[off_layer(d, LM + 1) + f * d.d_out + qo] = (__bf16)(pA[k] + pB[k]);
     }
   }
-  // the output bias (d_out = 1) and the loss partials: the point-threads (wave 0, lanes < FZ_PT) summed
+  // the output biases and the loss partials: the point-threads (wave 0, lanes < FZ_PT) summed
   if (w == 0) {
     const float bo = col4_sum(row16_sum(bo_acc));
-    if (l == 0) gs[off_layer(d, LM + 1) + W] = (__bf16)bo;
+    if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT] = (__bf16)bo;
+    if constexpr (DOUT > 1) {
+#pragma unroll
+      for (int qo = 1; qo < DOUT; ++qo) {
+        const float bq = col4_sum(row16_sum(bo_q[qo]));
+        if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT + qo] = (__bf16)bq;
+      }
+    }
 #pragma unroll
     for (int k = 0; k < LossF::NACC; ++k) {
       const float v = col4_sum(row16_sum(lacc[k]));

@@ -35,7 +35,7 @@ __host__ __device__ constexpr int fz3_slot_bytes(int WT, int S) {
 }
 // float area after the slots (FzFl): one set of partials, output-layer partial dots of 8 waves
 __host__ __device__ inline int fz3_lds_bytes(const NetDims& d, int WT, int S, int LM) {
-  return fz_nslot(LM) * fz3_slot_bytes(WT, S) + fz_fl(16 * WT, d.d_in, S, LM, FZ3_PT, 1, FZ_WAVES).total * 4;
+  return fz_nslot(LM) * fz3_slot_bytes(WT, S) + fz_fl(16 * WT, d.d_in, S, LM, FZ3_PT, 1, FZ_WAVES, d.d_out).total * 4;
 }
 
 // A fragments (hi + lo, every k-block) of one GEMM's weight-image rows.  In use: all issued at the
@@ -155,7 +155,7 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
   // the stream spec and input width as compile-time constants of the generated loss struct
   // (ops/fused_step.py spec_source): the one-hot stream selects and first-layer loops fold away
   constexpr JetSpec sp = LossF::SPEC;
-  constexpr int DIN = LossF::DIN;
+  constexpr int DIN = LossF::DIN, DOUT = LossF::DOUT;
   constexpr int W = 16 * WT, RS = bf3_img_rs(WT), SIMG = FZ3_PT * RS, SP = fz3_sp(S), VRS = fz3_vrs();
   constexpr int NR = WT / 4, NC = WT / 2;  // dK tiles per wave: row block (w >> 1), column block (w & 1)
   constexpr int SLOT = fz3_slot_bytes(WT, S), PT = FZ3_PT;
@@ -164,7 +164,7 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
   static_assert(SLOT % 16 == 0, "slot alignment");
   auto slot = [&](int k) { return reinterpret_cast<__bf16*>(lds_raw + k * SLOT); };
   // compile-time aux-image / LDS offsets, as fz_body: one partial set, output dots of all 8 waves
-  constexpr FzFl F = fz_fl(W, DIN, S, LM, PT, 1, FZ_WAVES);
+  constexpr FzFl F = fz_fl(W, DIN, S, LM, PT, 1, FZ_WAVES, DOUT);
   float* aux = reinterpret_cast<float*>(lds_raw + fz_nslot(LM) * SLOT);
   float *xs = aux + F.xs, *ubs = aux + F.ubs, *part = aux + F.part, *outp = aux + F.outp, *lpre = aux + F.lpre;
 
@@ -209,6 +209,9 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
   f32x4 dk[LM][NR][NC];
   float lacc[LossF::NACC];
   float bo_acc = 0.f;  // this point-thread's output-bias gradient (its points' value-stream dJ)
+  float bo_q[DOUT];    // ... of outputs 1.. of a network with several (bo_acc: output 0)
+#pragma unroll
+  for (int qo = 0; qo < DOUT; ++qo) bo_q[qo] = 0.f;
 #pragma unroll
   for (int k = 0; k < LossF::NACC; ++k) lacc[k] = 0.f;
 #pragma unroll
@@ -259,11 +262,22 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
       if (ly == LM) {  // output-layer partial dots of this wave's features -> LDS
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-          float a = 0.f;
+          if constexpr (DOUT == 1) {
+            float a = 0.f;
 #pragma unroll
-          for (int c = 0; c < 4; ++c) a = fmaf(h[s][c], Ko[(16 * o + 4 * g + c) * 4], a);
-          const float r = col4_sum(a);
-          if (g == 0) outp[(w * S + s) * PT + p] = r;
+            for (int c = 0; c < 4; ++c) a = fmaf(h[s][c], Ko[(16 * o + 4 * g + c) * 4], a);
+            const float r = col4_sum(a);
+            if (g == 0) outp[(w * S + s) * PT + p] = r;
+          } else {  // one dot per (stream, output), the outputs of a (stream, point) side by side
+#pragma unroll
+            for (int qo = 0; qo < DOUT; ++qo) {
+              float a = 0.f;
+#pragma unroll
+              for (int c = 0; c < 4; ++c) a = fmaf(h[s][c], Ko[(16 * o + 4 * g + c) * 4 + qo], a);
+              const float r = col4_sum(a);
+              if (g == 0) outp[((w * S + s) * PT + p) * DOUT + qo] = r;
+            }
+          }
         }
       }
       __syncthreads();
@@ -275,40 +289,85 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     // profiles/r6ag_jsum_ab.txt) -------------------------------------------------------------
     int tl = tid;
     asm volatile("" : "+v"(tl));
-    if (tl < S * PT) {
-      const int s = tl / PT, pt = tl - s * PT;
-      float a = outp[s * PT + pt];  // (fz_jsum, inline: the call reordered this kernel's schedule)
+    if constexpr (DOUT == 1) {
+      if (tl < S * PT) {
+        const int s = tl / PT, pt = tl - s * PT;
+        float a = outp[s * PT + pt];  // (fz_jsum, inline: the call reordered this kernel's schedule)
 #pragma unroll
-      for (int ww = 1; ww < FZ_WAVES; ++ww) a += outp[(ww * S + s) * PT + pt];
-      outp[s * PT + pt] = s == 0 ? a + aux[F.bo] : a;
+        for (int ww = 1; ww < FZ_WAVES; ++ww) a += outp[(ww * S + s) * PT + pt];
+        outp[s * PT + pt] = s == 0 ? a + aux[F.bo] : a;
+      }
+    } else {  // one thread per (stream, point, output): element tl of a wave's [S][PT][DOUT] set
+      static_assert(S * PT * DOUT <= 64 * FZ_WAVES / 2, "J sum: one thread per (stream, point, output)");
+      if (tl < S * PT * DOUT) {
+        float a = outp[tl];
+#pragma unroll
+        for (int ww = 1; ww < FZ_WAVES; ++ww) a += outp[ww * S * PT * DOUT + tl];
+        outp[tl] = tl < PT * DOUT ? a + aux[F.bo + tl % DOUT] : a;
+      }
     }
     __syncthreads();
     // ---- the per-point loss (generated) and its reverse sweep -> dJ into ubs ---------------
     tl = tid;
     asm volatile("" : "+v"(tl));
-    if (tl < PT) LossF::template eval<S, PT, 1>(outp, xs, tl, pb + tl, N, *P.lptrs, ubs, lacc, lpre[tl], 0.f);
+    if constexpr (DOUT == 1) {
+      if (tl < PT) LossF::template eval<S, PT, 1>(outp, xs, tl, pb + tl, N, *P.lptrs, ubs, lacc, lpre[tl], 0.f);
+    } else {
+      if (tl < PT)
+        LossF::template eval<S, PT, 1>(outp, xs, tl, pb + tl, N, *P.lptrs, ubs, lacc, lpre[tl], (const float*)nullptr);
+    }
     __syncthreads();
     FZ_TS(9);
     tl = tid;
     asm volatile("" : "+v"(tl));
     if (tl < PT) bo_acc += ubs[tl * 4];  // dbo: this point's value-stream dJ
+    if constexpr (DOUT > 1) {
+      if (tl < PT) {
+#pragma unroll
+        for (int qo = 1; qo < DOUT; ++qo) bo_q[qo] += ubs[tl * 4 + qo];
+      }
+    }
     // ---- reverse through the output layer: hb = Ko ub, dKo, the top tanh layer's adjoint ----
     {
       __bf16* im = slot(0);
       f32x4 h[S], hb[S], zb[S];
       fz3_get_h<WT, S>(im, L, o, h, fz3_vimg(im, WT, S) + voff);
-      f32x4 kq, pp = zero4();
+      if constexpr (DOUT == 1) {
+        f32x4 kq, pp = zero4();
 #pragma unroll
-      for (int c = 0; c < 4; ++c) kq[c] = Ko[(16 * o + 4 * g + c) * 4];
+        for (int c = 0; c < 4; ++c) kq[c] = Ko[(16 * o + 4 * g + c) * 4];
 #pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const float ub = ubs[(s * PT + p) * 4];
-        hb[s] = kq * ub;
-        pp += h[s] * ub;
-      }
-      {
-        const float r = row16_sum4(pp);
-        if ((p & 3) == 0) accKo[(16 * o + 4 * g + (p >> 2)) * 4] += r;
+        for (int s = 0; s < S; ++s) {
+          const float ub = ubs[(s * PT + p) * 4];
+          hb[s] = kq * ub;
+          pp += h[s] * ub;
+        }
+        {
+          const float r = row16_sum4(pp);
+          if ((p & 3) == 0) accKo[(16 * o + 4 * g + (p >> 2)) * 4] += r;
+        }
+      } else {  // hb[s] = sum_q Ko[.][q] ub[s][q]; dKo[.][q] += sum_s h[s] ub[s][q]
+        f32x4 kq[DOUT], pp[DOUT];
+#pragma unroll
+        for (int qo = 0; qo < DOUT; ++qo) {
+          pp[qo] = zero4();
+#pragma unroll
+          for (int c = 0; c < 4; ++c) kq[qo][c] = Ko[(16 * o + 4 * g + c) * 4 + qo];
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+#pragma unroll
+          for (int qo = 0; qo < DOUT; ++qo) {
+            const float ub = ubs[(s * PT + p) * 4 + qo];
+            hb[s] = qo == 0 ? kq[0] * ub : hb[s] + kq[qo] * ub;
+            pp[qo] += h[s] * ub;
+          }
+        }
+#pragma unroll
+        for (int qo = 0; qo < DOUT; ++qo) {
+          const float r = row16_sum4(pp[qo]);
+          if ((p & 3) == 0) accKo[(16 * o + 4 * g + (p >> 2)) * 4 + qo] += r;
+        }
       }
       tanh_jet_b<S, NSO>(sp, h, hb, zb);
       const float r = row16_sum4(zb[0]);
@@ -411,12 +470,24 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     gs[DIN * W + f] = part[f];  // b0
     for (int ly = 1; ly <= LM; ++ly) gs[off_layer(d, ly) + W * W + f] = part[ly * W + f];
     for (int j = 0; j < DIN; ++j) gs[j * W + f] = part[(LM + 1) * W + j * W + f];
-    gs[off_layer(d, LM + 1) + f] = part[(LM + 1 + DIN) * W + f * 4];
+    if constexpr (DOUT == 1) {
+      gs[off_layer(d, LM + 1) + f] = part[(LM + 1 + DIN) * W + f * 4];
+    } else {
+#pragma unroll
+      for (int qo = 0; qo < DOUT; ++qo) gs[off_layer(d, LM + 1) + f * DOUT + qo] = part[(LM + 1 + DIN) * W + f * 4 + qo];
+    }
   }
-  // the output bias and the loss partials: the point-threads (wave 0, lanes < PT) summed
+  // the output biases and the loss partials: the point-threads (wave 0, lanes < PT) summed
   if (w == 0) {
     const float bo = col4_sum(row16_sum(bo_acc));
-    if (l == 0) gs[off_layer(d, LM + 1) + W] = bo;
+    if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT] = bo;
+    if constexpr (DOUT > 1) {
+#pragma unroll
+      for (int qo = 1; qo < DOUT; ++qo) {
+        const float bq = col4_sum(row16_sum(bo_q[qo]));
+        if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT + qo] = bq;
+      }
+    }
 #pragma unroll
     for (int k = 0; k < LossF::NACC; ++k) {
       const float v = col4_sum(row16_sum(lacc[k]));

@@ -22,7 +22,15 @@ Precision ``bf16x3`` (the L-BFGS objective) runs the same one-launch structure w
 operand split into bf16 hi + lo (``csrc/jet_fused3.h``: 16-point tiles, since the lo planes double
 the LDS images); its tail reduces fp32 slab rows.
 
-``TDQ_FUSED_STEP=0`` keeps the separate launches (``fit.run_ranges``).
+Networks with 2-4 outputs (systems of PDEs) run on the same two kernels inside their geometry
+(width 128, 2-3 MFMA layers, S <= 4, plain programs): the number of outputs is a compile-time
+constant of the generated kernel (``GenLoss::DOUT``) - one output-layer dot per (stream, output), the
+loss's ``JV`` / ``UB`` take the output as a third argument, the reverse sums over the outputs.  A
+combination whose LDS does not fit (bf16, 3 MFMA layers, S = 4, 4 outputs) and every multi-output
+network outside the geometry keep the separate launches.
+
+``TDQ_FUSED_STEP=0`` keeps the separate launches (``fit.run_ranges``);
+``TDQ_FUSED_STEP_SYSTEMS=0`` does so for networks with several outputs only.
 """
 from __future__ import annotations
 
@@ -63,6 +71,12 @@ def enabled():
     return os.environ.get("TDQ_FUSED_STEP", "1") != "0"
 
 
+def systems_enabled():
+    """``TDQ_FUSED_STEP_SYSTEMS``: ``0`` keeps networks with several outputs on the separate launches
+    (:func:`ineligible` answers ``"d_out != 1"``)."""
+    return os.environ.get("TDQ_FUSED_STEP_SYSTEMS", "1") != "0"
+
+
 def _csrc():
     return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 
@@ -78,10 +92,11 @@ def header_source():
     return "\n".join(out)
 
 
-def spec_source(spec, S, d_in):
-    """``SPEC`` / ``DIN`` members of the generated struct: the plan's stream spec (csrc
-    jet_common.h ``make_spec``) and the input width as compile-time constants, so the kernel's
-    one-hot stream selects and first-layer loops fold away (the kernels require them)."""
+def spec_source(spec, S, d_in, d_out=1):
+    """``SPEC`` / ``DIN`` / ``DOUT`` members of the generated struct: the plan's stream spec (csrc
+    jet_common.h ``make_spec``), the input width and the number of network outputs as compile-time
+    constants, so the kernel's one-hot stream selects, first-layer loops and output-layer loops
+    fold away (the kernels require them)."""
     if spec is None or d_in is None:
         raise ValueError("gen_loss: the stream spec and d_in are compile-time constants of the kernel")
     M = 8   # TDQ_MAXS
@@ -101,10 +116,11 @@ def spec_source(spec, S, d_in):
     mat = lambda m: "{" + ", ".join("{" + ", ".join(f"{x:.1f}f" for x in r) + "}" for r in m) + "}"  # noqa: E731
     return [f"  static constexpr JetSpec SPEC = {{{arr(st)}, {arr(var)}, {mat(selA)}, {mat(selB)}, {arr(ia)}, "
             f"{arr(ib)}}};",
-            f"  static constexpr int DIN = {int(d_in)};"]
+            f"  static constexpr int DIN = {int(d_in)};",
+            f"  static constexpr int DOUT = {int(d_out)};"]
 
 
-def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None):
+def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None, d_out=1):
     """``struct GenLoss`` of the loss groups laid out in the fused point set.  ``groups``: one
     ``(program, start, n_slots, n)`` per group - its ``n`` instances occupy points ``start + k``
     (one slot) or the pairs ``start + 2k, start + 2k + 1`` (two slots: a periodic pair side by side,
@@ -113,12 +129,22 @@ def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None):
     from the next point-thread), per-point inputs (SA weights, data values, scalars) from global
     memory, loss / scalar-gradient sums into the thread's accumulators, dJ of the instance's points
     into the tile's ``ubs``.  Points outside every group get dJ = 0.  ``eval<S, PT>`` serves both
-    tile sizes (``PT`` points per tile)."""
+    tile sizes (``PT`` points per tile).
+
+    ``d_out`` > 1 (a system): a STREAM operand is ``stream | column << COL_SHIFT`` as in
+    :func:`.loss_jit._group_code_cols`; J is ``JV(stream, point, output)``, the adjoints are
+    ``dj{slot}_{stream}_{output}`` and EVERY output of every (slot, stream) is stored - zero where the
+    program reads nothing, so the kernel's reverse never sees a previous tile's value.  The
+    arithmetic statements are the same; with one output the emitted text is unchanged."""
+    D = int(d_out)
+    if not 1 <= D <= 4:
+        raise ValueError(f"fused step: {D} network outputs")
+    cmask = (1 << loss_jit.COL_SHIFT) - 1
     L = []
     e = L.append
     e("struct GenLoss {")
     e(f"  static constexpr int NACC = {max(1, nacc)};")
-    for ln in spec_source(spec, S, d_in):
+    for ln in spec_source(spec, S, d_in, D):
         e(ln)
 
     def branches(body):
@@ -165,11 +191,16 @@ def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None):
     e("  }")
     e("  template <int S, int PT, int NW>")
     e("  __device__ static void eval(const float* jv, const float* xs, int t, int n, int N, "
-      "const FzLossPtrs& ptr, float* ubs, float (&acc)[NACC], float pv, float bo) {")
+      "const FzLossPtrs& ptr, float* ubs, float (&acc)[NACC], float pv, "
+      + ("float bo" if D == 1 else "const float* bo") + ") {")
     # J of (stream, point): the NW waves' partial output dots summed here (wave order, + bo on the
     # value stream) instead of in a separate phase behind one more barrier
-    e("    #define JV(s_, k_) fz_jsum<S, PT, NW>(jv, (s_), (k_), bo)")
-    e("    #define UB(s_, k_) ubs[((s_) * PT + (k_)) * 4]")
+    if D == 1:
+        e("    #define JV(s_, k_) fz_jsum<S, PT, NW>(jv, (s_), (k_), bo)")
+        e("    #define UB(s_, k_) ubs[((s_) * PT + (k_)) * 4]")
+    else:
+        e(f"    #define JV(s_, k_, q_) fz_jsum_q<S, PT, NW, {D}>(jv, (s_), (k_), (q_), bo)")
+        e("    #define UB(s_, k_, q_) ubs[((s_) * PT + (k_)) * 4 + (q_)]")
 
     cur = {}
 
@@ -179,11 +210,19 @@ def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None):
         nr = max(1, P.n_regs)
         e("      float " + ", ".join(f"v{r}" for r in range(nr)) + ";")
         e("      float " + ", ".join(f"a{r} = 0.f" for r in range(nr)) + ";")
-        e("      float " + ", ".join(f"dj{sl}_{b} = 0.f" for sl in range(ns) for b in range(S)) + ";")
+        if D == 1:
+            e("      float " + ", ".join(f"dj{sl}_{b} = 0.f" for sl in range(ns) for b in range(S)) + ";")
+        else:
+            e("      float " + ", ".join(f"dj{sl}_{b}_{q} = 0.f" for sl in range(ns) for b in range(S)
+                                         for q in range(D)) + ";")
 
         def load(name, r, a, b):
             if name in ("STREAM", "COORD") and a >= ns:
                 raise ValueError("fused step: slot outside the group")
+            if name == "STREAM" and D > 1:
+                if (b & cmask) >= S or (b >> loss_jit.COL_SHIFT) >= D:
+                    raise ValueError("fused step: stream outside the jet plan")
+                return f"      v{r} = JV({b & cmask}, t + {a}, {b >> loss_jit.COL_SHIFT});"
             if name == "STREAM":
                 return f"      v{r} = JV({b}, t + {a});"
             if name == "COORD":
@@ -203,19 +242,29 @@ def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None):
 
         def store(name, r, a, b, g):
             if name == "STREAM":
-                if b >= S:
+                if (b & cmask) >= S:
                     raise ValueError("fused step: stream outside the jet plan")
+                if D > 1:
+                    return f"      dj{a}_{b & cmask}_{b >> loss_jit.COL_SHIFT} += {g};"
                 return f"      dj{a}_{b} += {g};"
             if name == "LAM":
                 return f"      ptr.dlam[{a}][i] = {g};"
             return f"      acc[{n_terms + a}] += {g};"
 
         loss_jit._reverse_code(P, e, store)
-        e("      " + " ".join(f"UB({b}, t + {sl}) = dj{sl}_{b};" for sl in range(ns) for b in range(S)))
+        if D == 1:
+            e("      " + " ".join(f"UB({b}, t + {sl}) = dj{sl}_{b};" for sl in range(ns) for b in range(S)))
+        else:
+            for sl in range(ns):
+                for b in range(S):
+                    e("      " + " ".join(f"UB({b}, t + {sl}, {q}) = dj{sl}_{b}_{q};" for q in range(D)))
 
     branches(eval_body)
     e("    #pragma unroll")
-    e("    for (int s = 0; s < S; ++s) UB(s, t) = 0.f;")
+    if D == 1:
+        e("    for (int s = 0; s < S; ++s) UB(s, t) = 0.f;")
+    else:
+        e("    for (int s = 0; s < S; ++s) { " + " ".join(f"UB(s, t, {q}) = 0.f;" for q in range(D)) + " }")
     e("    #undef JV")
     e("    #undef UB")
     e("  }")
@@ -378,7 +427,8 @@ def recipe(prog, fop, layout, precision=None):
         raise ValueError(f"fused step: {lds} bytes of LDS")
     source = None
     if layout is not None:
-        gen = gen_loss(layout, fop.n_terms, fop.n_terms + fop.n_scal, S, spec=spec, d_in=cfg["d_in"])
+        gen = gen_loss(layout, fop.n_terms, fop.n_terms + fop.n_scal, S, spec=spec, d_in=cfg["d_in"],
+                       d_out=cfg["d_out"])
         source = kernel_source(S, nso, LM, lds, gen, lo=lo)
     return KernelRecipe(cfg, S, spec, nso, LM, lo, 16 if lo else 32, lds, kernel_name(lo), source)
 
@@ -420,7 +470,16 @@ def ineligible(prog, fop):
     if cfg["precision"] not in ("bf16", "bf16x3") or not jet_hip.is_split_bf16(cfg):
         return f"precision {cfg['precision']}"
     if cfg["d_out"] != 1:
-        return "d_out != 1"
+        # a system: inside the kernels' geometry (width 128, 2-3 MFMA layers, S <= 4, up to 4 outputs,
+        # no high-order boundary streams) unless switched off; every other multi-output network keeps
+        # the separate launches with this answer
+        if not (systems_enabled() and cfg["d_out"] <= 4 and not _mixed(prog) and cfg["S"] <= 4
+                and cfg["n_hidden"] - 1 in (2, 3) and all(w == 128 for w in cfg["widths"])):
+            return "d_out != 1"
+        try:
+            recipe(prog, fop, None)
+        except ValueError as e:
+            return f"LDS: {e} ({cfg['precision']}, {cfg['n_hidden']} hidden layers, S={cfg['S']}, d_out={cfg['d_out']})"
     try:
         recipe(prog, fop, None)
     except ValueError:
