@@ -359,10 +359,13 @@ __device__ __forceinline__ float fz_jsum_q(const float* jv, int s, int k, int q,
 }
 
 // ---- Steps of the tile loop that fz_body below (32-point tiles) and fz3_body of jet_fused3.h
-// (16-point tiles) share, beside FzFl, fz_h0, fz_tr and fz_jsum above.  The other steps the two
-// bodies have in common (the tile fetch, the accumulator zeroing, the output-layer dots and
-// adjoint, the layer-0 partials, the slab epilogue) stay written out in both: as shared functions
-// each changed the generated code of one of the kernels (profiles/r9_fused_refactor.md).
+// (16-point tiles) share, beside FzFl, fz_h0, fz_tr and fz_jsum above.  The number of network
+// outputs DOUT (1-4) is a loop bound in both bodies - one output is the one-trip case, not a second
+// copy.  The other steps the two bodies have in common (the tile fetch, the accumulator zeroing,
+// the output-layer dots and adjoint, the layer-0 partials, the slab epilogue) stay written out in
+// both: as shared functions the tile fetch and the dots slowed the bf16 step by ~1 % each on the
+// GPU, the adjoint costs tdq_fused_step3 a VGPR spill (profiles/r12_fused_fold.md; the earlier,
+// assembly-identical step: profiles/r9_fused_refactor.md).
 
 // This thread's element of a PT-point tile's inputs (fetched one tile ahead) -> LDS: coordinate j
 // of point pt on thread pt * TDQ_MAXD + j, the loss's first per-point input on the PT threads after
@@ -467,8 +470,7 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
   fz_setup<WT, LM, F.xs>(P, aux, tid);
   f32x4 dk[LM][NR][NC];
   float lacc[LossF::NACC];  // this point-thread's loss / scalar-gradient sums (all tiles)
-  float bo_acc = 0.f;  // this point-thread's output-bias gradient (its points' value-stream dJ)
-  float bo_q[DOUT];    // ... of outputs 1.. of a network with several (bo_acc: output 0)
+  float bo_q[DOUT];  // this point-thread's output-bias gradients (its points' value-stream dJ, per output)
 #pragma unroll
   for (int qo = 0; qo < DOUT; ++qo) bo_q[qo] = 0.f;
 #pragma unroll
@@ -540,31 +542,21 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
       }
       if (ly == LM) {  // output-layer partial dots of this wave's features -> LDS
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-          if constexpr (DOUT == 1) {
-            float a = 0.f;
+        for (int s = 0; s < S; ++s) {  // one dot per (stream, output), the outputs of a (stream, point) side by side
+          float a[DOUT];
 #pragma unroll
-            for (int oo = 0; oo < OPW; ++oo)
+          for (int qo = 0; qo < DOUT; ++qo) a[qo] = 0.f;
 #pragma unroll
-              for (int c = 0; c < 4; ++c) a = fmaf(hq[oo][s][c], Ko[(16 * (o0 + oo) + 4 * g + c) * 4], a);
-            const float r = col4_sum(a);
-            if (g == 0) outp[(wo * S + s) * FZ_PT + row] = r;
-          } else {  // one dot per (stream, output), the outputs of a (stream, point) side by side
-            float a[DOUT];
+          for (int oo = 0; oo < OPW; ++oo)
 #pragma unroll
-            for (int qo = 0; qo < DOUT; ++qo) a[qo] = 0.f;
+            for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int oo = 0; oo < OPW; ++oo)
+              for (int qo = 0; qo < DOUT; ++qo)
+                a[qo] = fmaf(hq[oo][s][c], Ko[(16 * (o0 + oo) + 4 * g + c) * 4 + qo], a[qo]);
 #pragma unroll
-              for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int qo = 0; qo < DOUT; ++qo)
-                  a[qo] = fmaf(hq[oo][s][c], Ko[(16 * (o0 + oo) + 4 * g + c) * 4 + qo], a[qo]);
-#pragma unroll
-            for (int qo = 0; qo < DOUT; ++qo) {
-              const float r = col4_sum(a[qo]);
-              if (g == 0) outp[((wo * S + s) * FZ_PT + row) * DOUT + qo] = r;
-            }
+          for (int qo = 0; qo < DOUT; ++qo) {
+            const float r = col4_sum(a[qo]);
+            if (g == 0) outp[((wo * S + s) * FZ_PT + row) * DOUT + qo] = r;
           }
         }
       }
@@ -591,12 +583,9 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
     // four lanes of wave 0 used to hold that wave - and the next barrier - for ~1-2k cycles)
     tl = tid;
     asm volatile("" : "+v"(tl));
-    if (tl < PT) bo_acc += ubs[tl * 4];
-    if constexpr (DOUT > 1) {
-      if (tl < PT) {
+    if (tl < PT) {
 #pragma unroll
-        for (int qo = 1; qo < DOUT; ++qo) bo_q[qo] += ubs[tl * 4 + qo];
-      }
+      for (int qo = 0; qo < DOUT; ++qo) bo_q[qo] += ubs[tl * 4 + qo];
     }
     // ---- reverse through the output layer: hb = Ko ub, dKo, the top tanh layer's adjoint ----
 #pragma unroll
@@ -605,42 +594,27 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
       __bf16* im = slot(ZS);
       f32x4 h[S], hb[S], zb[S];
       fz_get_h<WT, S>(im, L, q, to, h);
-      if constexpr (DOUT == 1) {
-        f32x4 kq, pp = zero4();
+      // hb[s] = sum_q Ko[.][q] ub[s][q]; dKo[.][q] += sum_s h[s] ub[s][q]
+      f32x4 kq[DOUT], pp[DOUT];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) kq[c] = Ko[(16 * to + 4 * g + c) * 4];
+      for (int qo = 0; qo < DOUT; ++qo) {
+        pp[qo] = zero4();
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-          const float ub = ubs[(s * FZ_PT + row) * 4];
-          hb[s] = kq * ub;
-          pp += h[s] * ub;
-        }
-        {
-          const float r = row16_sum4(pp);
-          if ((p & 3) == 0) accKo[(16 * to + 4 * g + (p >> 2)) * 4] += r;
-        }
-      } else {  // hb[s] = sum_q Ko[.][q] ub[s][q]; dKo[.][q] += sum_s h[s] ub[s][q]
-        f32x4 kq[DOUT], pp[DOUT];
+        for (int c = 0; c < 4; ++c) kq[qo][c] = Ko[(16 * to + 4 * g + c) * 4 + qo];
+      }
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
 #pragma unroll
         for (int qo = 0; qo < DOUT; ++qo) {
-          pp[qo] = zero4();
-#pragma unroll
-          for (int c = 0; c < 4; ++c) kq[qo][c] = Ko[(16 * to + 4 * g + c) * 4 + qo];
+          const float ub = ubs[(s * FZ_PT + row) * 4 + qo];
+          hb[s] = qo == 0 ? kq[0] * ub : hb[s] + kq[qo] * ub;
+          pp[qo] += h[s] * ub;
         }
+      }
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-#pragma unroll
-          for (int qo = 0; qo < DOUT; ++qo) {
-            const float ub = ubs[(s * FZ_PT + row) * 4 + qo];
-            hb[s] = qo == 0 ? kq[0] * ub : hb[s] + kq[qo] * ub;
-            pp[qo] += h[s] * ub;
-          }
-        }
-#pragma unroll
-        for (int qo = 0; qo < DOUT; ++qo) {
-          const float r = row16_sum4(pp[qo]);
-          if ((p & 3) == 0) accKo[(16 * to + 4 * g + (p >> 2)) * 4 + qo] += r;
-        }
+      for (int qo = 0; qo < DOUT; ++qo) {
+        const float r = row16_sum4(pp[qo]);
+        if ((p & 3) == 0) accKo[(16 * to + 4 * g + (p >> 2)) * 4 + qo] += r;
       }
       tanh_jet_b<S, NSO>(sp, h, hb, zb);
       const float r = row16_sum4(zb[0]);
@@ -773,21 +747,18 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
       const int k = (LM + 1) * W + j * W + f;
       gs[j * W + f] = (__bf16)(pA[k] + pB[k]);
     }
-    for (int qo = 0; qo < d.d_out; ++qo) {
+#pragma unroll
+    for (int qo = 0; qo < DOUT; ++qo) {
       const int k = (LM + 1 + DIN) * W + f * 4 + qo;
-      gs[off_layer(d, LM + 1) + f * d.d_out + qo] = (__bf16)(pA[k] + pB[k]);
+      gs[off_layer(d, LM + 1) + f * DOUT + qo] = (__bf16)(pA[k] + pB[k]);
     }
   }
   // the output biases and the loss partials: the point-threads (wave 0, lanes < FZ_PT) summed
   if (w == 0) {
-    const float bo = col4_sum(row16_sum(bo_acc));
-    if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT] = (__bf16)bo;
-    if constexpr (DOUT > 1) {
 #pragma unroll
-      for (int qo = 1; qo < DOUT; ++qo) {
-        const float bq = col4_sum(row16_sum(bo_q[qo]));
-        if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT + qo] = (__bf16)bq;
-      }
+    for (int qo = 0; qo < DOUT; ++qo) {
+      const float bq = col4_sum(row16_sum(bo_q[qo]));
+      if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT + qo] = (__bf16)bq;
     }
 #pragma unroll
     for (int k = 0; k < LossF::NACC; ++k) {

@@ -208,8 +208,7 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
   }
   f32x4 dk[LM][NR][NC];
   float lacc[LossF::NACC];
-  float bo_acc = 0.f;  // this point-thread's output-bias gradient (its points' value-stream dJ)
-  float bo_q[DOUT];    // ... of outputs 1.. of a network with several (bo_acc: output 0)
+  float bo_q[DOUT];  // this point-thread's output-bias gradients (its points' value-stream dJ, per output)
 #pragma unroll
   for (int qo = 0; qo < DOUT; ++qo) bo_q[qo] = 0.f;
 #pragma unroll
@@ -261,22 +260,14 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
       fz3_put_h<WT, S>(im, L, o, h, fz3_vimg(im, WT, S) + voff);
       if (ly == LM) {  // output-layer partial dots of this wave's features -> LDS
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-          if constexpr (DOUT == 1) {
+        for (int s = 0; s < S; ++s) {  // one dot per (stream, output), the outputs of a (stream, point) side by side
+#pragma unroll
+          for (int qo = 0; qo < DOUT; ++qo) {
             float a = 0.f;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) a = fmaf(h[s][c], Ko[(16 * o + 4 * g + c) * 4], a);
+            for (int c = 0; c < 4; ++c) a = fmaf(h[s][c], Ko[(16 * o + 4 * g + c) * 4 + qo], a);
             const float r = col4_sum(a);
-            if (g == 0) outp[(w * S + s) * PT + p] = r;
-          } else {  // one dot per (stream, output), the outputs of a (stream, point) side by side
-#pragma unroll
-            for (int qo = 0; qo < DOUT; ++qo) {
-              float a = 0.f;
-#pragma unroll
-              for (int c = 0; c < 4; ++c) a = fmaf(h[s][c], Ko[(16 * o + 4 * g + c) * 4 + qo], a);
-              const float r = col4_sum(a);
-              if (g == 0) outp[((w * S + s) * PT + p) * DOUT + qo] = r;
-            }
+            if (g == 0) outp[((w * S + s) * PT + p) * DOUT + qo] = r;
           }
         }
       }
@@ -289,22 +280,15 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     // profiles/r6ag_jsum_ab.txt) -------------------------------------------------------------
     int tl = tid;
     asm volatile("" : "+v"(tl));
-    if constexpr (DOUT == 1) {
-      if (tl < S * PT) {
-        const int s = tl / PT, pt = tl - s * PT;
-        float a = outp[s * PT + pt];  // (fz_jsum, inline: the call reordered this kernel's schedule)
+    // one thread per (stream, point, output): element tl of a wave's [S][PT][DOUT] set.  (The bound
+    // is the several-output path's; one output needs only S * PT <= 512 threads and has at most
+    // TDQ_MAXS * PT = 128.)
+    static_assert(S * PT * DOUT <= 64 * FZ_WAVES / 2, "J sum: one thread per (stream, point, output)");
+    if (tl < S * PT * DOUT) {
+      float a = outp[tl];
 #pragma unroll
-        for (int ww = 1; ww < FZ_WAVES; ++ww) a += outp[(ww * S + s) * PT + pt];
-        outp[s * PT + pt] = s == 0 ? a + aux[F.bo] : a;
-      }
-    } else {  // one thread per (stream, point, output): element tl of a wave's [S][PT][DOUT] set
-      static_assert(S * PT * DOUT <= 64 * FZ_WAVES / 2, "J sum: one thread per (stream, point, output)");
-      if (tl < S * PT * DOUT) {
-        float a = outp[tl];
-#pragma unroll
-        for (int ww = 1; ww < FZ_WAVES; ++ww) a += outp[ww * S * PT * DOUT + tl];
-        outp[tl] = tl < PT * DOUT ? a + aux[F.bo + tl % DOUT] : a;
-      }
+      for (int ww = 1; ww < FZ_WAVES; ++ww) a += outp[ww * S * PT * DOUT + tl];
+      outp[tl] = tl < PT * DOUT ? a + aux[F.bo + tl % DOUT] : a;
     }
     __syncthreads();
     // ---- the per-point loss (generated) and its reverse sweep -> dJ into ubs ---------------
@@ -320,54 +304,36 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     FZ_TS(9);
     tl = tid;
     asm volatile("" : "+v"(tl));
-    if (tl < PT) bo_acc += ubs[tl * 4];  // dbo: this point's value-stream dJ
-    if constexpr (DOUT > 1) {
-      if (tl < PT) {
+    if (tl < PT) {  // dbo: this point's value-stream dJ
 #pragma unroll
-        for (int qo = 1; qo < DOUT; ++qo) bo_q[qo] += ubs[tl * 4 + qo];
-      }
+      for (int qo = 0; qo < DOUT; ++qo) bo_q[qo] += ubs[tl * 4 + qo];
     }
     // ---- reverse through the output layer: hb = Ko ub, dKo, the top tanh layer's adjoint ----
     {
       __bf16* im = slot(0);
       f32x4 h[S], hb[S], zb[S];
       fz3_get_h<WT, S>(im, L, o, h, fz3_vimg(im, WT, S) + voff);
-      if constexpr (DOUT == 1) {
-        f32x4 kq, pp = zero4();
+      // hb[s] = sum_q Ko[.][q] ub[s][q]; dKo[.][q] += sum_s h[s] ub[s][q]
+      f32x4 kq[DOUT], pp[DOUT];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) kq[c] = Ko[(16 * o + 4 * g + c) * 4];
+      for (int qo = 0; qo < DOUT; ++qo) {
+        pp[qo] = zero4();
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-          const float ub = ubs[(s * PT + p) * 4];
-          hb[s] = kq * ub;
-          pp += h[s] * ub;
-        }
-        {
-          const float r = row16_sum4(pp);
-          if ((p & 3) == 0) accKo[(16 * o + 4 * g + (p >> 2)) * 4] += r;
-        }
-      } else {  // hb[s] = sum_q Ko[.][q] ub[s][q]; dKo[.][q] += sum_s h[s] ub[s][q]
-        f32x4 kq[DOUT], pp[DOUT];
+        for (int c = 0; c < 4; ++c) kq[qo][c] = Ko[(16 * o + 4 * g + c) * 4 + qo];
+      }
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
 #pragma unroll
         for (int qo = 0; qo < DOUT; ++qo) {
-          pp[qo] = zero4();
-#pragma unroll
-          for (int c = 0; c < 4; ++c) kq[qo][c] = Ko[(16 * o + 4 * g + c) * 4 + qo];
+          const float ub = ubs[(s * PT + p) * 4 + qo];
+          hb[s] = qo == 0 ? kq[0] * ub : hb[s] + kq[qo] * ub;
+          pp[qo] += h[s] * ub;
         }
+      }
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-#pragma unroll
-          for (int qo = 0; qo < DOUT; ++qo) {
-            const float ub = ubs[(s * PT + p) * 4 + qo];
-            hb[s] = qo == 0 ? kq[0] * ub : hb[s] + kq[qo] * ub;
-            pp[qo] += h[s] * ub;
-          }
-        }
-#pragma unroll
-        for (int qo = 0; qo < DOUT; ++qo) {
-          const float r = row16_sum4(pp[qo]);
-          if ((p & 3) == 0) accKo[(16 * o + 4 * g + (p >> 2)) * 4 + qo] += r;
-        }
+      for (int qo = 0; qo < DOUT; ++qo) {
+        const float r = row16_sum4(pp[qo]);
+        if ((p & 3) == 0) accKo[(16 * o + 4 * g + (p >> 2)) * 4 + qo] += r;
       }
       tanh_jet_b<S, NSO>(sp, h, hb, zb);
       const float r = row16_sum4(zb[0]);
@@ -470,23 +436,15 @@ __device__ __forceinline__ void fz3_body(const FzParams& P, char* lds_raw) {
     gs[DIN * W + f] = part[f];  // b0
     for (int ly = 1; ly <= LM; ++ly) gs[off_layer(d, ly) + W * W + f] = part[ly * W + f];
     for (int j = 0; j < DIN; ++j) gs[j * W + f] = part[(LM + 1) * W + j * W + f];
-    if constexpr (DOUT == 1) {
-      gs[off_layer(d, LM + 1) + f] = part[(LM + 1 + DIN) * W + f * 4];
-    } else {
 #pragma unroll
-      for (int qo = 0; qo < DOUT; ++qo) gs[off_layer(d, LM + 1) + f * DOUT + qo] = part[(LM + 1 + DIN) * W + f * 4 + qo];
-    }
+    for (int qo = 0; qo < DOUT; ++qo) gs[off_layer(d, LM + 1) + f * DOUT + qo] = part[(LM + 1 + DIN) * W + f * 4 + qo];
   }
   // the output biases and the loss partials: the point-threads (wave 0, lanes < PT) summed
   if (w == 0) {
-    const float bo = col4_sum(row16_sum(bo_acc));
-    if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT] = bo;
-    if constexpr (DOUT > 1) {
 #pragma unroll
-      for (int qo = 1; qo < DOUT; ++qo) {
-        const float bq = col4_sum(row16_sum(bo_q[qo]));
-        if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT + qo] = bq;
-      }
+    for (int qo = 0; qo < DOUT; ++qo) {
+      const float bq = col4_sum(row16_sum(bo_q[qo]));
+      if (l == 0) gs[off_layer(d, LM + 1) + W * DOUT + qo] = bq;
     }
 #pragma unroll
     for (int k = 0; k < LossF::NACC; ++k) {

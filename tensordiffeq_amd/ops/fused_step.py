@@ -132,14 +132,25 @@ def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None, d_out=1):
     tile sizes (``PT`` points per tile).
 
     ``d_out`` > 1 (a system): a STREAM operand is ``stream | column << COL_SHIFT`` as in
-    :func:`.loss_jit._group_code_cols`; J is ``JV(stream, point, output)``, the adjoints are
+    :func:`.loss_jit._group_code`; J is ``JV(stream, point, output)``, the adjoints are
     ``dj{slot}_{stream}_{output}`` and EVERY output of every (slot, stream) is stored - zero where the
-    program reads nothing, so the kernel's reverse never sees a previous tile's value.  The
-    arithmetic statements are the same; with one output the emitted text is unchanged."""
+    program reads nothing, so the kernel's reverse never sees a previous tile's value.  With one
+    output the output suffix / argument drops (``dj`` / ``jv`` / ``ub`` below) and the bias comes by
+    value: the text such a program had before systems were served."""
     D = int(d_out)
     if not 1 <= D <= 4:
         raise ValueError(f"fused step: {D} network outputs")
     cmask = (1 << loss_jit.COL_SHIFT) - 1
+
+    def dj(sl, s, q):   # the adjoint of J(slot, stream, output)
+        return f"dj{sl}_{s}" + (f"_{q}" if D > 1 else "")
+
+    def jv(s, k, q):
+        return f"JV({s}, {k}" + (f", {q})" if D > 1 else ")")
+
+    def ub(s, k, q):
+        return f"UB({s}, {k}" + (f", {q})" if D > 1 else ")")
+
     L = []
     e = L.append
     e("struct GenLoss {")
@@ -189,12 +200,13 @@ def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None, d_out=1):
         kw = "else if"
     e("    return 0.f;")
     e("  }")
+    # the kernel's side of the interface (csrc/jet_fused.h): J of (stream, point[, output]) is the NW
+    # waves' partial output dots summed here (wave order, + bo on the value stream) instead of in a
+    # separate phase behind one more barrier; one output takes its bias by value, several the array
     e("  template <int S, int PT, int NW>")
     e("  __device__ static void eval(const float* jv, const float* xs, int t, int n, int N, "
       "const FzLossPtrs& ptr, float* ubs, float (&acc)[NACC], float pv, "
       + ("float bo" if D == 1 else "const float* bo") + ") {")
-    # J of (stream, point): the NW waves' partial output dots summed here (wave order, + bo on the
-    # value stream) instead of in a separate phase behind one more barrier
     if D == 1:
         e("    #define JV(s_, k_) fz_jsum<S, PT, NW>(jv, (s_), (k_), bo)")
         e("    #define UB(s_, k_) ubs[((s_) * PT + (k_)) * 4]")
@@ -210,21 +222,21 @@ def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None, d_out=1):
         nr = max(1, P.n_regs)
         e("      float " + ", ".join(f"v{r}" for r in range(nr)) + ";")
         e("      float " + ", ".join(f"a{r} = 0.f" for r in range(nr)) + ";")
-        if D == 1:
-            e("      float " + ", ".join(f"dj{sl}_{b} = 0.f" for sl in range(ns) for b in range(S)) + ";")
-        else:
-            e("      float " + ", ".join(f"dj{sl}_{b}_{q} = 0.f" for sl in range(ns) for b in range(S)
-                                         for q in range(D)) + ";")
+        e("      float " + ", ".join(f"{dj(sl, b, q)} = 0.f" for sl in range(ns) for b in range(S)
+                                     for q in range(D)) + ";")
+
+        def stream(b):
+            s, q = b & cmask, b >> loss_jit.COL_SHIFT
+            if s >= S or q >= D:
+                raise ValueError("fused step: stream outside the jet plan")
+            return s, q
 
         def load(name, r, a, b):
             if name in ("STREAM", "COORD") and a >= ns:
                 raise ValueError("fused step: slot outside the group")
-            if name == "STREAM" and D > 1:
-                if (b & cmask) >= S or (b >> loss_jit.COL_SHIFT) >= D:
-                    raise ValueError("fused step: stream outside the jet plan")
-                return f"      v{r} = JV({b & cmask}, t + {a}, {b >> loss_jit.COL_SHIFT});"
             if name == "STREAM":
-                return f"      v{r} = JV({b}, t + {a});"
+                s, q = stream(b)
+                return f"      v{r} = {jv(s, f't + {a}', q)};"
             if name == "COORD":
                 return f"      v{r} = xs[(t + {a}) * TDQ_MAXD + {b}];"
             if (name, a) == cur["first"] and not cur["used"]:
@@ -242,29 +254,22 @@ def gen_loss(groups, n_terms, nacc, S, spec=None, d_in=None, d_out=1):
 
         def store(name, r, a, b, g):
             if name == "STREAM":
-                if (b & cmask) >= S:
-                    raise ValueError("fused step: stream outside the jet plan")
-                if D > 1:
-                    return f"      dj{a}_{b & cmask}_{b >> loss_jit.COL_SHIFT} += {g};"
-                return f"      dj{a}_{b} += {g};"
+                return f"      {dj(a, *stream(b))} += {g};"
             if name == "LAM":
                 return f"      ptr.dlam[{a}][i] = {g};"
             return f"      acc[{n_terms + a}] += {g};"
 
         loss_jit._reverse_code(P, e, store)
-        if D == 1:
-            e("      " + " ".join(f"UB({b}, t + {sl}) = dj{sl}_{b};" for sl in range(ns) for b in range(S)))
-        else:
-            for sl in range(ns):
-                for b in range(S):
-                    e("      " + " ".join(f"UB({b}, t + {sl}, {q}) = dj{sl}_{b}_{q};" for q in range(D)))
+        # the outputs of one (slot, stream) on one line (one output: all of them on one)
+        rows = [" ".join(f"{ub(b, f't + {sl}', q)} = {dj(sl, b, q)};" for q in range(D))
+                for sl in range(ns) for b in range(S)]
+        for ln in ([" ".join(rows)] if D == 1 else rows):
+            e("      " + ln)
 
     branches(eval_body)
     e("    #pragma unroll")
-    if D == 1:
-        e("    for (int s = 0; s < S; ++s) UB(s, t) = 0.f;")
-    else:
-        e("    for (int s = 0; s < S; ++s) { " + " ".join(f"UB(s, t, {q}) = 0.f;" for q in range(D)) + " }")
+    zero = " ".join(f"{ub('s', 't', q)} = 0.f;" for q in range(D))
+    e("    for (int s = 0; s < S; ++s) " + (zero if D == 1 else "{ " + zero + " }"))
     e("    #undef JV")
     e("    #undef UB")
     e("  }")

@@ -10,7 +10,7 @@ interpreter's statement for the same opcode and the kernel is compiled with stat
 contraction only, with the interpreter's grid, block mapping, block reductions and output order:
 the two produce the same bits (tests/test_loss_jit_gpu.py).
 
-Networks with several outputs (:func:`_group_code_cols`): the ``d_out`` components of one (stream,
+Networks with several outputs (:func:`_group_code` with ``D`` > 1): the ``d_out`` components of one (stream,
 point) are contiguous in ``J`` and ``dJ``, so for 2 and 4 outputs the kernel reads them with one 8- /
 16-byte load where the program first touches that (stream, point), and writes the adjoints - zeros
 for the components the program does not read - with one 8- / 16-byte store; 3 outputs use scalar
@@ -155,61 +155,14 @@ def _reverse_code(P, e, store):
             e(f"    a{a} += 2.f * {g} * v{a};")
 
 
-def _group_code(P, gi_meta, n_points, S, d_in, n_terms):
-    """Straight-line body of one segment group (mirrors loss_fused_kernel statement by statement)."""
-    block_off, phase, n, seg_off, n_slots, loaded = gi_meta
-    L = []
-    e = L.append
-    e(f"    const int i = (blk - {block_off}) * {LF_BLOCK} + tid - {phase};")
-    e(f"    const bool active = i >= 0 && i < {n};")
-    e("    const int ii = active ? i : 0;")
-    nr = max(1, P.n_regs)
-    e("    float " + ", ".join(f"v{r}" for r in range(nr)) + ";")
-    e("    float " + ", ".join(f"a{r} = 0.f" for r in range(nr)) + ";")
-
-    def load(name, r, a, b):
-        # (``a`` is a segment slot for STREAM / COORD only, a value / weight / scalar id otherwise)
-        if name == "STREAM":
-            return f"    v{r} = J[(size_t){b} * {n_points} + {seg_off[a]} + ii];"
-        if name == "COORD":
-            return f"    v{r} = X[(size_t)({seg_off[a]} + ii) * {d_in} + {b}];"
-        return {"VAL": f"    v{r} = ptr.val[{a}][ii];",
-                "LAM": f"    v{r} = ptr.lam[{a}][ii];",
-                "SCAL": f"    v{r} = *ptr.scal[{a}];"}[name]
-
-    _forward_code(P, e, load)
-    for (f, w, t, c) in P.outputs:
-        cl = _lit(c)
-        e(f"    {{ const float f = v{f}, w = v{w};")
-        e(f"      const float contrib = active ? {cl} * w * f * f : 0.f;")
-        e("      const float s = block_sum(contrib, red);")
-        e(f"      if (tid == 0) acc[{t}] += s;")
-        e(f"      if (active) {{ a{f} += 2.f * {cl} * w * f; a{w} += {cl} * f * f; }} }}")
-
-    def store(name, r, a, b, g):
-        if name == "STREAM":
-            return f"    if (active) dJ[(size_t){b} * {n_points} + {seg_off[a]} + i] = {g};"
-        if name == "LAM":
-            return f"    if (active) ptr.dlam[{a}][i] = {g};"
-        return f"    {{ const float s = block_sum(active ? {g} : 0.f, red); if (tid == 0) acc[{n_terms + a}] += s; }}"
-
-    _reverse_code(P, e, store)
-    # dJ of every (point, stream) the program does not read is written as 0
-    zero = []
-    for sl in range(n_slots):
-        for s in range(S):
-            if not (loaded[sl] >> s) & 1:
-                zero.append(f"dJ[(size_t){s} * {n_points} + {seg_off[sl]} + i] = 0.f;")
-    if zero:
-        e("    if (active) { " + " ".join(zero) + " }")
-    return "\n".join(L)
-
-
-def _group_code_cols(P, gi_meta, n_points, S, d_in, n_terms, D):
-    """:func:`_group_code` for a network with ``D`` > 1 outputs (J / dJ: [stream][point][output])."""
+def _group_code(P, gi_meta, n_points, S, d_in, n_terms, D=1):
+    """Straight-line body of one segment group (mirrors loss_fused_kernel statement by statement).
+    The J / dJ accesses are the only part that depends on the network's outputs ``D``: with one, a
+    scalar ``J[...]`` per read, the adjoint stored where it is complete and the unread streams
+    zero-filled; with several (J / dJ: [stream][point][output]) every output of a (stream, point) in
+    one 8- / 16-byte access for 2 / 4 outputs, fetched at its first read and stored at the end."""
     block_off, phase, n, seg_off, n_slots, loaded = gi_meta
     vec = {2: "float2", 4: "float4"}.get(D)
-    comp = "xyzw"
     L = []
     e = L.append
     e(f"    const int i = (blk - {block_off}) * {LF_BLOCK} + tid - {phase};")
@@ -225,12 +178,15 @@ def _group_code_cols(P, gi_meta, n_points, S, d_in, n_terms, D):
         return f"((size_t){s} * {n_points} + {seg_off[slot]} + {idx}) * {D}"
 
     def load(name, r, a, b):
+        # (``a`` is a segment slot for STREAM / COORD only, a value / weight / scalar id otherwise)
         if name == "COORD":
             return f"    v{r} = X[(size_t)({seg_off[a]} + ii) * {d_in} + {b}];"
         if name != "STREAM":
             return {"VAL": f"    v{r} = ptr.val[{a}][ii];",
                     "LAM": f"    v{r} = ptr.lam[{a}][ii];",
                     "SCAL": f"    v{r} = *ptr.scal[{a}];"}[name]
+        if D == 1:
+            return f"    v{r} = J[(size_t){b} * {n_points} + {seg_off[a]} + ii];"
         s, q = b & ((1 << COL_SHIFT) - 1), b >> COL_SHIFT
         cols.setdefault((a, s), {})[q] = r
         if vec is None:
@@ -239,7 +195,7 @@ def _group_code_cols(P, gi_meta, n_points, S, d_in, n_terms, D):
         if (a, s) not in fetched:   # every output of this (stream, point) in one access
             fetched.add((a, s))
             out = f"    const {vec} j{a}_{s} = *reinterpret_cast<const {vec}*>(J + {elem(s, a, 'ii')});\n"
-        return out + f"    v{r} = j{a}_{s}.{comp[q]};"
+        return out + f"    v{r} = j{a}_{s}.{'xyzw'[q]};"
 
     _forward_code(P, e, load)
     for (f, w, t, c) in P.outputs:
@@ -251,6 +207,8 @@ def _group_code_cols(P, gi_meta, n_points, S, d_in, n_terms, D):
         e(f"      if (active) {{ a{f} += 2.f * {cl} * w * f; a{w} += {cl} * f * f; }} }}")
 
     def store(name, r, a, b, g):
+        if name == "STREAM" and D == 1:
+            return f"    if (active) dJ[(size_t){b} * {n_points} + {seg_off[a]} + i] = {g};"
         if name == "STREAM":   # written with the other outputs of its (stream, point) below
             return f"    // a{r}: dJ of stream {b & ((1 << COL_SHIFT) - 1)}, output {b >> COL_SHIFT}, slot {a}"
         if name == "LAM":
@@ -258,17 +216,22 @@ def _group_code_cols(P, gi_meta, n_points, S, d_in, n_terms, D):
         return f"    {{ const float s = block_sum(active ? {g} : 0.f, red); if (tid == 0) acc[{n_terms + a}] += s; }}"
 
     _reverse_code(P, e, store)
-    # dJ of every (stream, point) of the group's slots: the adjoint of each output the program read,
-    # 0 for the others
     st = []
     for sl in range(n_slots):
         for s in range(S):
+            if D == 1:   # dJ of every (point, stream) the program does not read is written as 0
+                if not (loaded[sl] >> s) & 1:
+                    st.append(f"dJ[(size_t){s} * {n_points} + {seg_off[sl]} + i] = 0.f;")
+                continue
+            # dJ of every (stream, point): the adjoint of each output the program read, 0 for the others
             vals = [f"a{cols[(sl, s)][q]}" if q in cols.get((sl, s), {}) else "0.f" for q in range(D)]
             if vec is None:
                 st += [f"dJ[{elem(s, sl, 'i')} + {q}] = {v};" for q, v in enumerate(vals)]
             else:
                 st.append(f"*reinterpret_cast<{vec}*>(dJ + {elem(s, sl, 'i')}) = make_{vec}({', '.join(vals)});")
-    if st:
+    if st and D == 1:
+        e("    if (active) { " + " ".join(st) + " }")
+    elif st:
         e("    if (active) {\n      " + "\n      ".join(st) + "\n    }")
     return "\n".join(L)
 
@@ -294,8 +257,7 @@ def generate(op):
         lo, hi = meta[0], op.group_meta[k + 1][0] if k + 1 < len(op.group_meta) else op.n_blocks
         kw = "if" if k == 0 else "else if"
         out.append(f"  {kw} (blk < {hi}) {{  // group {k}: blocks [{lo}, {hi})")
-        out.append(_group_code(gr.program, meta, N, S, d_in, n_terms) if D == 1 else
-                   _group_code_cols(gr.program, meta, N, S, d_in, n_terms, D))
+        out.append(_group_code(gr.program, meta, N, S, d_in, n_terms, D))
         out.append("  }")
     out.append("  __syncthreads();")
     if nacc:

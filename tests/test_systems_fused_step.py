@@ -225,6 +225,32 @@ PARENT_BODIES = [
 ]
 
 
+# sha256 of ``fused_step.gen_loss`` and of ``loss_jit.generate`` for the NLS system on [2, 128 x 3, d_out],
+# computed on the commit before the two emitters folded their one-output / several-output forks
+PARENT_SYSTEM_SHA = {
+    2: ("c71a97b6930fc9dced3585c54cceda44e6b9544af33237a9e16759e6a846a5d6",
+        "8fb3246d8582ce00c4d1bb98b81fb7bc16f566967f86950698dd1ee4ac67e579"),
+    3: ("801ac6f1abe48b6547ac3ed3dfb1e596084ca9c486c455c440ff38846e686ce7",
+        "b2b2256fe49bae54966c21081837fed12b06517d4421145fa50b3b3e373ae7bf"),
+    4: ("b6b09c20abec23370cc8a3fb57401381cb8ff0576121373ba3f16a480c1ab2e4",
+        "e1b8338bcbdbb5ce0b84d6b7c6be3e49744459d82b5e949e4eabb3403f70b142"),
+}
+
+
+@pytest.mark.parametrize("d_out", [2, 3, 4])
+def test_system_generated_text_unchanged(d_out):
+    """The generated loss of the one-launch step and the specialised loss kernel of a system are
+    byte for byte what the parent commit emitted (2 / 4 outputs: vector J accesses, 3: scalar)."""
+    import hashlib
+    from tensordiffeq_amd.ops import fused_step, jet_hip, loss_jit
+    prog, op = _prog_op(nls_net("cpu", "jet", L3, d_out))
+    layout, _, _ = fused_step.point_layout(prog, fused_step.fused_groups(prog, op))
+    gen = fused_step.gen_loss(layout, op.n_terms, op.n_terms + op.n_scal, prog.plan.S,
+                              spec=jet_hip.stream_spec(prog.plan), d_in=2, d_out=d_out)
+    sha = lambda s: hashlib.sha256(s.encode()).hexdigest()  # noqa: E731
+    assert (sha(gen), sha(loss_jit.generate(op))) == PARENT_SYSTEM_SHA[d_out]
+
+
 def _group_bodies(gen):
     out, cur = [], None
     for ln in gen.splitlines():
