@@ -216,7 +216,8 @@ __device__ __forceinline__ void hi_tanh_b(const HiSpec& sp, const float (&z)[S],
 //   W [HI_W][HI_WS]          one layer's weights (row stride 132: the 8-float MFMA fragment rows
 //                            of 16 lanes land on distinct banks)
 //   A 2 x [HI_NP][S][HI_AB]  the workgroup's activations / adjoints as MFMA A rows, split once into
-//                            bf16 hi and lo at the store (every wave reads the same rows)
+//                            bf16 hi and lo at the store (every wave reads the same rows); a third
+//                            plane (lo2) for the three-way split of deep networks (HI_X3_DEPTH)
 //   R [HI_MR][HI_AS]         GEMM product (rows point * S + stream; both 16-row MFMA tiles)
 //   V [HI_TG][nvs][HI_W]     (chain) vector-parameter partials (nvs slots, hi_nvs)
 constexpr int HI_MR = 32;  // GEMM rows: HI_NP points x at most HI_MAXS streams
@@ -233,16 +234,27 @@ struct HiLds {
   __device__ float& w(int k, int f) const { return W[k * HI_WS + f]; }
   __device__ __bf16* ah() const { return reinterpret_cast<__bf16*>(A); }
   __device__ __bf16* al() const { return reinterpret_cast<__bf16*>(A) + HI_NP * S * HI_AB; }
+  __device__ __bf16* a2() const { return reinterpret_cast<__bf16*>(A) + 2 * HI_NP * S * HI_AB; }
 };
-__host__ __device__ inline size_t hi_lds_floats(int S, int nvs) {
-  return (size_t)HI_W * HI_WS + (size_t)HI_NP * S * HI_AB + (size_t)HI_MR * HI_AS + (size_t)HI_TG * nvs * HI_W;
+// The layer GEMMs' operands are split into two bf16 terms (three products, ~1e-5 per GEMM).  Each
+// GEMM's rounding is independent, so the error of a deep network grows with its depth: 16 hidden
+// layers (15 GEMMs each way) reach 2.5e-4 on a gradient block, past the family's 1e-4
+// (profiles/r13_jet_hi_oracle_errors.txt).  Networks with more than HI_X3_DEPTH hidden layers
+// therefore split into three terms (six products: fp32-exact operands); up to that depth - the
+// reference's networks - the kernels are the two-term ones, bit for bit.
+#define HI_X3_DEPTH 4
+__host__ __device__ inline bool hi_x3(int n_hidden) { return n_hidden > HI_X3_DEPTH; }
+// floats of the A rows: two (three: x3) bf16 planes of HI_AB per row
+__host__ __device__ inline size_t hi_a_floats(int S, bool x3) { return (size_t)HI_NP * S * HI_AB * (x3 ? 3 : 2) / 2; }
+__host__ __device__ inline size_t hi_lds_floats(int S, int nvs, bool x3) {
+  return (size_t)HI_W * HI_WS + hi_a_floats(S, x3) + (size_t)HI_MR * HI_AS + (size_t)HI_TG * nvs * HI_W;
 }
-__device__ inline HiLds hi_lds_map(float* base, int S) {
+__device__ inline HiLds hi_lds_map(float* base, int S, bool x3) {
   HiLds L;
   L.S = S;
   L.W = base;
   L.A = L.W + HI_W * HI_WS;
-  L.R = L.A + HI_NP * S * HI_AB;  // (two bf16 arrays = HI_AB floats per row)
+  L.R = L.A + hi_a_floats(S, x3);
   L.V = L.R + HI_MR * HI_AS;
   return L;
 }
@@ -327,6 +339,8 @@ __device__ __forceinline__ size_t hi_row(int layer, int n, int s, int S, int N) 
 // ~1e-5 relative).  Rows m = point * S + stream (at most 32: two 16-row tiles, rows >= 4 S zero);
 // wave w owns the 16 output columns [16 w, 16 w + 16).  Lane l: A[row l & 15][k = 8 (l >> 4) + j],
 // B[k][col l & 15], C[4 (l >> 4) + r][l & 15].  The product lands in R as [m][HI_AS].
+// Networks deeper than HI_X3_DEPTH take a third term per operand and the three products of the next
+// order (X3 instantiations; hi_split2, hi_mma3x).
 typedef __bf16 hbf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void hi_split(const float (&x)[8], hbf16x8& h, hbf16x8& lo) {
 #pragma unroll
@@ -342,11 +356,32 @@ __device__ __forceinline__ f32x4 hi_mma3(const hbf16x8& ah, const hbf16x8& al, c
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
 }
+// three-way split (deep networks): third term of x, and the three products of the next order
+// (lo lo, hi lo2, lo2 hi; what is left is below 2^-24 of |a| |b|), smallest first into a sum of their own
+__device__ __forceinline__ void hi_split2(const float (&x)[8], hbf16x8& l2) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const __bf16 hx = (__bf16)x[j];
+    const float r = x[j] - (float)hx;
+    const __bf16 lx = (__bf16)r;
+    l2[j] = (__bf16)(r - (float)lx);
+  }
+}
+__device__ __forceinline__ f32x4 hi_mma3x(const hbf16x8& ah, const hbf16x8& al, const hbf16x8& a2, const hbf16x8& bh,
+                                          const hbf16x8& bl, const hbf16x8& b2, f32x4 c) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bl, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b2, c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, bh, c, 0, 0, 0);
+}
 // element (m, k) of the A rows, split into bf16 hi + lo (hi_split's rounding)
+template <bool X3>
 __device__ __forceinline__ void hi_put_a(const HiLds& L, int m, int k, float x) {
   const __bf16 hx = (__bf16)x;
   L.ah()[m * HI_AB + k] = hx;
-  L.al()[m * HI_AB + k] = (__bf16)(x - (float)hx);
+  const float r = x - (float)hx;
+  const __bf16 lx = (__bf16)r;
+  L.al()[m * HI_AB + k] = lx;
+  if constexpr (X3) L.a2()[m * HI_AB + k] = (__bf16)(r - (float)lx);
 }
 // A fragment (row m, columns k0 .. k0 + 7) of the workgroup, hi and lo; rows past 4 S read as zero
 __device__ __forceinline__ void hi_arow(const HiLds& L, int m, int k0, int S, hbf16x8& h, hbf16x8& lo) {
@@ -357,12 +392,19 @@ __device__ __forceinline__ void hi_arow(const HiLds& L, int m, int k0, int S, hb
   h = in ? u : z;
   lo = in ? v : z;
 }
+__device__ __forceinline__ void hi_arow2(const HiLds& L, int m, int k0, int S, hbf16x8& l2) {
+  const bool in = m < HI_NP * S;
+  const hbf16x8 u = *reinterpret_cast<const hbf16x8*>(L.a2() + (in ? m : 0) * HI_AB + k0);
+  const hbf16x8 z = {};
+  l2 = in ? u : z;
+}
 // TRANS = false (forward): out[m][c] = sum_k A[m][k] W[k][c]; true (adjoint chain): out[m][c] =
 // sum_o A[m][o] W[c][o]
-template <bool TRANS>
+template <bool TRANS, bool X3>
 __device__ __forceinline__ void hi_mma(const HiLds& L, int S, int kin) {
   const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, p = l & 15, g = l >> 4, col = 16 * wv + p;
   f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f};  // X3: the small products
   const int nk = (kin + 31) >> 5;
   for (int kk = 0; kk < nk; ++kk) {
     const int k0 = 32 * kk + 8 * g;
@@ -385,6 +427,18 @@ __device__ __forceinline__ void hi_mma(const HiLds& L, int S, int kin) {
     hi_split(w, wh, wl);
     c0 = hi_mma3(a0h, a0l, wh, wl, c0);
     c1 = hi_mma3(a1h, a1l, wh, wl, c1);
+    if constexpr (X3) {
+      hbf16x8 a02, a12, w2;
+      hi_arow2(L, p, k0, S, a02);
+      hi_arow2(L, 16 + p, k0, S, a12);
+      hi_split2(w, w2);
+      e0 = hi_mma3x(a0h, a0l, a02, wh, wl, w2, e0);
+      e1 = hi_mma3x(a1h, a1l, a12, wh, wl, w2, e1);
+    }
+  }
+  if constexpr (X3) {
+    c0 += e0;
+    c1 += e1;
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -395,13 +449,13 @@ __device__ __forceinline__ void hi_mma(const HiLds& L, int S, int kin) {
 
 // thread t: point p = t >> 7 and feature f = t & 127 in the elementwise phases; in the GEMM, feature
 // quad f4 = (t >> 2) & 31 and k-quarter ks = t & 3 (so f = 4 f4 + ks)
-template <int S, bool CH>
+template <int S, bool CH, bool X3>
 __global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) jet_hi_fwd_kernel(const float* __restrict__ X, int N,
                                                                 const float* __restrict__ P, NetDims d, HiSpec sp,
                                                                 float* __restrict__ J, int ldJ, int j0,
                                                                 float* __restrict__ Zb, float* __restrict__ Hb) {
   extern __shared__ __attribute__((aligned(16))) float hi_lds[];
-  const HiLds L = hi_lds_map(hi_lds, S);
+  const HiLds L = hi_lds_map(hi_lds, S, X3);
   HI_TS_DECL
   HI_TS()
   const int t = threadIdx.x, f = t & (HI_W - 1), pg = t >> 7;
@@ -448,7 +502,7 @@ __global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu
     if (i >= 1) {  // z_i = h_{i-1} W_i (+ b_i); W_{i+1} loads in flight meanwhile
       if (i + 1 < Lh) hi_get_w(wr, P, d, i + 1);
       float b = P[off_layer(d, i) + hw(d, i - 1) * wi + (f < wi ? f : wi - 1)];  // masked after the GEMM
-      hi_mma<false>(L, S, hw(d, i - 1));
+      hi_mma<false, X3>(L, S, hw(d, i - 1));
       HI_TS()
       __syncthreads();  // z in R; every GEMM read of A / W done
       b = f < wi ? b : 0.f;
@@ -474,7 +528,7 @@ __global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu
       }
 #pragma unroll
       for (int s = 0; s < S; ++s) {
-        hi_put_a(L, pg * S + s, f, h[s]);
+        hi_put_a<X3>(L, pg * S + s, f, h[s]);
         hl[s] = h[s];
       }
     }
@@ -559,14 +613,14 @@ __device__ __forceinline__ void hi_vsum(const HiLds& L, float* __restrict__ vrow
 // zb_i -> Bb (the hidden-to-hidden kernels' gradients are jet_hi_wgrad_kernel's); the vector
 // parameters' gradients are summed over the workgroup's points here -> vslab row blockIdx.x.
 // Thread t: point p = t >> 7, feature f = t & 127; the GEMM is hi_mma's (wave w: columns 16 w ..).
-template <int S, bool CH>
+template <int S, bool CH, bool X3>
 __global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) jet_hi_chain_kernel(int N, const float* __restrict__ P, NetDims d,
                                                                   HiSpec sp, const float* __restrict__ X,
                                                                   const float* __restrict__ dJ, int ldJ,
                                                                   int j0, const float* __restrict__ Zb,
                                                                   float* __restrict__ Bb, float* __restrict__ vslab) {
   extern __shared__ __attribute__((aligned(16))) float hi_lds[];
-  const HiLds L = hi_lds_map(hi_lds, S);
+  const HiLds L = hi_lds_map(hi_lds, S, X3);
   HI_TS_DECL
   HI_TS()
   const int t = threadIdx.x, pg = t >> 7, f = t & (HI_W - 1);
@@ -643,7 +697,7 @@ __global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu
         for (int s = 0; s < S; ++s) Bb[hi_row(i, n, s, S, N) + f] = zb[s];
       }
 #pragma unroll
-      for (int s = 0; s < S; ++s) hi_put_a(L, pg * S + s, f, zb[s]);
+      for (int s = 0; s < S; ++s) hi_put_a<X3>(L, pg * S + s, f, zb[s]);
       // vector-parameter partials of this point (padding points: zero adjoints already)
       float* V = L.V + pg * nvs * HI_W;
       V[f] = ok ? zb[0] : 0.f;
@@ -683,7 +737,7 @@ __global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
     for (int s = 0; s < S; ++s) z[s] = Zb[hi_row(i - 1, n, s, S, N) + f];  // used (masked) after the GEMM
     __builtin_amdgcn_sched_barrier(0);
-    hi_mma<true>(L, S, wi);
+    hi_mma<true, X3>(L, S, wi);
     HI_TS()
     __syncthreads();  // hb in R; GEMM reads of A / W done
     {
@@ -895,35 +949,37 @@ void hi_attr(K* kern) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)HI_LDS_MAX);
 }
-bool hi_lds_fits(int S, const NetDims& d) { return hi_lds_floats(S, hi_nvs(d)) * sizeof(float) <= HI_LDS_MAX; }
+bool hi_lds_fits(int S, const NetDims& d) {
+  return hi_lds_floats(S, hi_nvs(d), hi_x3(d.n_hidden)) * sizeof(float) <= HI_LDS_MAX;
+}
 
 int hi_splits(int N) { return std::min(HI_KS, std::max(1, (N + 63) / 64)); }
 
-template <int S, bool CH>
+template <int S, bool CH, bool X3>
 int hi_launch_fwd(const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp, float* J, int ldJ, int j0,
                   float* Zb, float* Hb, hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    hi_attr(&jet_hi_fwd_kernel<S, CH>);
+    hi_attr(&jet_hi_fwd_kernel<S, CH, X3>);
     attr = true;
   }
-  hipLaunchKernelGGL((jet_hi_fwd_kernel<S, CH>), dim3((N + HI_NP - 1) / HI_NP), dim3(HI_THREADS),
-                     hi_lds_floats(S, 0) * sizeof(float), st,
+  hipLaunchKernelGGL((jet_hi_fwd_kernel<S, CH, X3>), dim3((N + HI_NP - 1) / HI_NP), dim3(HI_THREADS),
+                     hi_lds_floats(S, 0, X3) * sizeof(float), st,
                      X, N, P, d, sp, J, ldJ, j0, Zb, Hb);
   TDQ_CHECK_LAUNCH();
   return 0;
 }
 
-template <int S, bool CH>
+template <int S, bool CH, bool X3>
 int hi_launch_chain(int N, const float* P, const NetDims& d, const HiSpec& sp, const float* X, const float* dJ,
                     int ldJ, int j0, const float* Zb, float* Bb, float* vslab, hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    hi_attr(&jet_hi_chain_kernel<S, CH>);
+    hi_attr(&jet_hi_chain_kernel<S, CH, X3>);
     attr = true;
   }
-  hipLaunchKernelGGL((jet_hi_chain_kernel<S, CH>), dim3((N + HI_NP - 1) / HI_NP), dim3(HI_THREADS),
-                     hi_lds_floats(S, hi_nvs(d)) * sizeof(float), st, N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab);
+  hipLaunchKernelGGL((jet_hi_chain_kernel<S, CH, X3>), dim3((N + HI_NP - 1) / HI_NP), dim3(HI_THREADS),
+                     hi_lds_floats(S, hi_nvs(d), X3) * sizeof(float), st, N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab);
   TDQ_CHECK_LAUNCH();
   return 0;
 }
@@ -935,9 +991,11 @@ int hi_launch_chain(int N, const float* P, const NetDims& d, const HiSpec& sp, c
 
 int hi_fwd(const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp, float* J, int ldJ, int j0,
            float* Zb, float* Hb, hipStream_t st) {
-  const bool ch = sp.chain != 0;
-#define HI_F(SS, CC) \
-  if (sp.S == SS && ch == CC) return hi_launch_fwd<SS, CC>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st);
+  const bool ch = sp.chain != 0, x3 = hi_x3(d.n_hidden);
+#define HI_F(SS, CC)                                                                                  \
+  if (sp.S == SS && ch == CC)                                                                         \
+    return x3 ? hi_launch_fwd<SS, CC, true>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st)                   \
+              : hi_launch_fwd<SS, CC, false>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st);
   HI_CASES(HI_F)
 #undef HI_F
   return (int)hipErrorInvalidValue;
@@ -945,9 +1003,11 @@ int hi_fwd(const float* X, int N, const float* P, const NetDims& d, const HiSpec
 
 int hi_chain(int N, const float* P, const NetDims& d, const HiSpec& sp, const float* X, const float* dJ, int ldJ,
              int j0, const float* Zb, float* Bb, float* vslab, hipStream_t st) {
-  const bool ch = sp.chain != 0;
-#define HI_B(SS, CC) \
-  if (sp.S == SS && ch == CC) return hi_launch_chain<SS, CC>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st);
+  const bool ch = sp.chain != 0, x3 = hi_x3(d.n_hidden);
+#define HI_B(SS, CC)                                                                                  \
+  if (sp.S == SS && ch == CC)                                                                         \
+    return x3 ? hi_launch_chain<SS, CC, true>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st)         \
+              : hi_launch_chain<SS, CC, false>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st);
   HI_CASES(HI_B)
 #undef HI_B
   return (int)hipErrorInvalidValue;
