@@ -31,6 +31,13 @@ nan_check              TDQ_NAN_CHECK=0 disables    device loss-history NaN/Inf s
 (split)                TDQ_SPLIT                   auto (cut at 0.38 for bf16, 0.35 for bf16x3) | off | cut
                                                    fraction: two point ranges on concurrent graph
                                                    branches (fit.point_ranges)
+(hi_kernel)            TDQ_HI_KERNEL=0 disables    high-order (order 3 / 4) jet kernels: those points'
+                                                   streams on the torch jet (models/loss.py)
+(hi_scratch)           TDQ_HI_SCRATCH_BYTES        byte cap of the high-order kernels' activation scratch
+                                                   (default 32 GiB); above it a residual with order-3/4
+                                                   derivatives keeps the torch jet backend (ops/jet_hi.py)
+(hi_tile)              TDQ_HI_TILE                 auto | 4 | 8 | 16: points per workgroup of the
+                                                   high-order kernels (auto: 8 from 20,000 points on)
 (lbfgs_fused)          TDQ_LBFGS_FUSED=0           five-launch L-BFGS update instead of two
 (profiling)            TDQ_PROFILE                 directory: every fit() runs under torch.profiler
                                                    -> trace.json + kernels.txt (profiling.py)

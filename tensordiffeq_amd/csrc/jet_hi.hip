@@ -36,6 +36,9 @@
 // behind it).  The stream count is a template parameter, and the common plan - the
 // univariate chain u, u_v, u_vv, u_vvv(, u_vvvv) of the reference's periodic BCs - has its tanh jet
 // and adjoint as straight-line code; other plans interpret the partition table.
+// Large point sets (a residual with u_xxx / u_xxxx: every collocation point is a high-order point)
+// take the tile kernels further down (8 / 16 points per workgroup, tdq_jet_hi_tile_* entry points);
+// the three kernels and the entry points of the small sets stay as they are for every N.
 // History (AC-baseline, 402 points, order 4; profiles/): interpreted 256-thread first build
 // 0.31 + 0.40 ms per step; this layout 26 + 57 us isolated (profiles/r4g_kernel_stats_hi_isolated.txt);
 // MFMA layer GEMMs: chain -16 %, forward -7 % of workgroup cycles (profiles/r4x_hi_phase_stamps_mfma.txt);
@@ -891,6 +894,388 @@ __global__ void __launch_bounds__(256) jet_hi_reduce_kernel(const float* __restr
     hi_vec_reduce(blockIdx.x - ntb, vslab, nwg, Vst, d, grad);
 }
 
+// ---- Large point sets (KdV-type residuals: the high-order points are the whole collocation set,
+// 10^4 - 10^6 of them; bandwidth, not latency, is the budget) ------------------------------------
+// The 4-point kernels above reload a 64 KB layer of weights per layer for 4 points.  The tile kernels
+// below serve NP = 8 or 16 points per workgroup with the same thread layout: each of the HI_TG
+// thread groups carries PT = NP / HI_TG points through the elementwise phases (local point
+// j HI_TG + group), the GEMM covers the NP S rows in 16-row MFMA tiles, and a wave fetches and
+// splits each weight fragment once per k-block for all its row tiles.  Per row the arithmetic is
+// that of the 4-point kernels (k order, the three / six products, hi_sigmas, chain / table code, the
+// output layer's sum), so a row's streams are those of the 4-point kernels bit for bit.
+//
+// LDS (bytes): W 67,584 + A NP S 272 (2 | 3 planes) + R 16 ceil(NP S / 16) 528 + V 2,048 nvs (chain
+// only; nvs = hi_nvs: 3 for d_in <= 2, d_out = 1, up to 9).  Largest NP that fits HI_LDS_MAX =
+// 163,840 (forward / chain at nvs = 3 / chain at nvs = 9):
+//
+//     S      two-term split (<= 4 hidden layers)          three-term split
+//     2, 3   16 / 16 / 16                                 16 / 16 / 16
+//     4      16 / 16 / 16  (136,192 / 142,336 / 154,624)  16 / 16 / 8  (153,600 / 159,744 / 172,032)
+//     5      16 / 16 /  8  (153,344 / 159,488 / 171,776)   8 /  8 / 8
+//     6       8 /  8 /  8                                  8 /  8 / 8
+//     7       8 /  8 /  8                                  8 /  8 / 4  (8: 147,072 / 153,216 / 165,504)
+//     8       8 /  8 /  8  (136,192 / 142,336 / 154,624)   8 /  8 / 4  (8: 153,600 / 159,744 / 172,032)
+//
+// (per instantiation, with registers and spills: profiles/r14_jet_hi_tile_resources.txt)
+// (R aliases nothing: every area is live across a GEMM - W and A are its operands, V waits for the
+// hi_vsum after it - so there is no dead area that would buy a size.)  hi_t_fits is the test; the
+// host picks the tile of the forward and of the chain separately (ops/jet_hi.py).
+template <int NP>
+struct HiLdsT : HiLds {
+  __device__ __bf16* al() const { return reinterpret_cast<__bf16*>(A) + NP * S * HI_AB; }
+  __device__ __bf16* a2() const { return reinterpret_cast<__bf16*>(A) + 2 * NP * S * HI_AB; }
+};
+__host__ __device__ constexpr int hi_t_rows(int NP, int S) { return (NP * S + 15) / 16 * 16; }
+__host__ __device__ constexpr size_t hi_t_a_floats(int NP, int S, bool x3) {
+  return (size_t)NP * S * HI_AB * (x3 ? 3 : 2) / 2;
+}
+__host__ __device__ constexpr size_t hi_t_lds_floats(int NP, int S, int nvs, bool x3) {
+  return (size_t)HI_W * HI_WS + hi_t_a_floats(NP, S, x3) + (size_t)hi_t_rows(NP, S) * HI_AS +
+         (size_t)HI_TG * nvs * HI_W;
+}
+template <int NP>
+__device__ inline HiLdsT<NP> hi_lds_map_t(float* base, int S, bool x3) {
+  HiLdsT<NP> L;
+  L.S = S;
+  L.W = base;
+  L.A = L.W + HI_W * HI_WS;
+  L.R = L.A + hi_t_a_floats(NP, S, x3);
+  L.V = L.R + hi_t_rows(NP, S) * HI_AS;
+  return L;
+}
+template <bool X3, int NP>
+__device__ __forceinline__ void hi_put_a_t(const HiLdsT<NP>& L, int m, int k, float x) {
+  const __bf16 hx = (__bf16)x;
+  L.ah()[m * HI_AB + k] = hx;
+  const float r = x - (float)hx;
+  const __bf16 lx = (__bf16)r;
+  L.al()[m * HI_AB + k] = lx;
+  if constexpr (X3) L.a2()[m * HI_AB + k] = (__bf16)(r - (float)lx);
+}
+// hi_mma over MT = ceil(NP S / 16) row tiles: the weight fragment of a k-block is fetched and split
+// once for all of them; rows past NP S read as zero; R has 16 MT rows
+template <bool TRANS, bool X3, int NP, int S>
+__device__ __forceinline__ void hi_mma_t(const HiLdsT<NP>& L, int kin) {
+  constexpr int MT = hi_t_rows(NP, S) / 16;
+  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, p = l & 15, g = l >> 4, col = 16 * wv + p;
+  f32x4 c[MT], e[X3 ? MT : 1];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) c[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int mt = 0; mt < (X3 ? MT : 1); ++mt) e[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int nk = (kin + 31) >> 5;
+  const hbf16x8 zero = {};
+  for (int kk = 0; kk < nk; ++kk) {
+    const int k0 = 32 * kk + 8 * g;
+    float w[8];
+    hbf16x8 wh, wl, w2;
+    if constexpr (TRANS) {
+      const float* r = &L.w(col, k0);
+      const f32x4 u = *reinterpret_cast<const f32x4*>(r), v = *reinterpret_cast<const f32x4*>(r + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        w[j] = u[j];
+        w[4 + j] = v[j];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) w[j] = L.w(k0 + j, col);
+    }
+    hi_split(w, wh, wl);
+    if constexpr (X3) hi_split2(w, w2);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      const int m = 16 * mt + p;
+      const bool in = m < NP * S;
+      const int o = (in ? m : 0) * HI_AB + k0;
+      hbf16x8 ah = *reinterpret_cast<const hbf16x8*>(L.ah() + o), al = *reinterpret_cast<const hbf16x8*>(L.al() + o);
+      ah = in ? ah : zero;
+      al = in ? al : zero;
+      c[mt] = hi_mma3(ah, al, wh, wl, c[mt]);
+      if constexpr (X3) {
+        hbf16x8 a2 = *reinterpret_cast<const hbf16x8*>(L.a2() + o);
+        a2 = in ? a2 : zero;
+        e[mt] = hi_mma3x(ah, al, a2, wh, wl, w2, e[mt]);
+      }
+    }
+  }
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    if constexpr (X3) c[mt] += e[mt];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) L.R[(16 * mt + 4 * g + r) * HI_AS + col] = c[mt][r];
+  }
+}
+
+// forward, NP points per workgroup: thread (f, group pg) owns feature f of the local points
+// j HI_TG + pg, j < PT
+template <int S, bool CH, bool X3, int NP>
+__global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
+jet_hi_fwd_tile_kernel(const float* __restrict__ X, int N, const float* __restrict__ P, NetDims d, HiSpec sp,
+                       float* __restrict__ J, int ldJ, int j0, float* __restrict__ Zb, float* __restrict__ Hb) {
+  constexpr int PT = NP / HI_TG;
+  static_assert(NP % HI_TG == 0 && NP * S <= HI_W, "the output layer's products take NP S rows of the weight area");
+  extern __shared__ __attribute__((aligned(16))) float hi_lds[];
+  const HiLdsT<NP> L = hi_lds_map_t<NP>(hi_lds, S, X3);
+  const int t = threadIdx.x, f = t & (HI_W - 1), pg = t >> 7;
+  const int Lh = d.n_hidden;
+  bool ok[PT];
+  int n[PT];
+#pragma unroll
+  for (int j = 0; j < PT; ++j) {
+    const int m = blockIdx.x * NP + j * HI_TG + pg;
+    ok[j] = m < N;
+    n[j] = ok[j] ? m : N - 1;
+  }
+  HiWRegs wr;
+  if (Lh > 1) hi_get_w(wr, P, d, 1);
+  float z[PT][S], h[PT][S];
+  {  // layer 0
+    const int w0 = hw(d, 0);
+    const int fc = f < w0 ? f : w0 - 1;
+    float xv[PT][TDQ_MAXD], kv[TDQ_MAXD];
+#pragma unroll
+    for (int v = 0; v < TDQ_MAXD; ++v) {
+      const int vc = v < d.d_in ? v : d.d_in - 1;
+      kv[v] = P[vc * w0 + fc];
+#pragma unroll
+      for (int j = 0; j < PT; ++j) xv[j][v] = X[(size_t)n[j] * d.d_in + vc];
+    }
+    float b0 = P[d.d_in * w0 + fc];
+    __builtin_amdgcn_sched_barrier(0);  // all loads in flight first
+#pragma unroll
+    for (int v = 0; v < TDQ_MAXD; ++v) kv[v] = (v < d.d_in && f < w0) ? kv[v] : 0.f;
+    b0 = f < w0 ? b0 : 0.f;
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
+      float a = b0;
+#pragma unroll
+      for (int v = 0; v < TDQ_MAXD; ++v) a = fmaf(v < d.d_in ? xv[j][v] : 0.f, kv[v], a);
+      z[j][0] = a;
+#pragma unroll
+      for (int s = 1; s < S; ++s) {
+        float k1 = 0.f;
+#pragma unroll
+        for (int v = 0; v < TDQ_MAXD; ++v) k1 = sp.var[s] == v ? kv[v] : k1;
+        z[j][s] = sp.order[s] == 1 ? k1 : 0.f;
+      }
+    }
+  }
+  if (Lh > 1) hi_put_w(L, wr, d, 1);
+  for (int i = 0; i < Lh; ++i) {
+    const int wi = hw(d, i);
+    if (i >= 1) {  // z_i = h_{i-1} W_i (+ b_i); W_{i+1} loads in flight meanwhile
+      if (i + 1 < Lh) hi_get_w(wr, P, d, i + 1);
+      float b = P[off_layer(d, i) + hw(d, i - 1) * wi + (f < wi ? f : wi - 1)];  // masked after the GEMM
+      hi_mma_t<false, X3, NP, S>(L, hw(d, i - 1));
+      __syncthreads();  // z in R; every GEMM read of A / W done
+      b = f < wi ? b : 0.f;
+#pragma unroll
+      for (int j = 0; j < PT; ++j)
+#pragma unroll
+        for (int s = 0; s < S; ++s) z[j][s] = L.R[((j * HI_TG + pg) * S + s) * HI_AS + f] + (s == 0 ? b : 0.f);
+      if (i + 1 < Lh) hi_put_w(L, wr, d, i + 1);
+    }
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
+      if (f < wi) {
+        hi_tanh_f<S, CH>(sp, z[j], h[j]);
+      } else {
+#pragma unroll
+        for (int s = 0; s < S; ++s) h[j][s] = 0.f;
+      }
+      if (ok[j]) {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+          Zb[hi_row(i, n[j], s, S, N) + f] = z[j][s];
+          Hb[hi_row(i, n[j], s, S, N) + f] = h[j][s];
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < S; ++s) hi_put_a_t<X3, NP>(L, (j * HI_TG + pg) * S + s, f, h[j][s]);
+    }
+    __syncthreads();  // A (and W) of the next GEMM written; R read
+  }
+  // ---- output layer, one output q at a time: per-feature products of the NP S rows into the free
+  // weight area, then one thread per (point, stream) sums them (the 4-point kernel's sum)
+  const int wl = hw(d, Lh - 1), dout = d.d_out;
+  const float* Ko = P + off_layer(d, Lh);
+  float* part = L.W;  // [local point][s][HI_W]
+  for (int q = 0; q < dout; ++q) {
+    const float ko = ldm(Ko + (f < wl ? f : wl - 1) * dout + q, f < wl);
+#pragma unroll
+    for (int j = 0; j < PT; ++j)
+#pragma unroll
+      for (int s = 0; s < S; ++s) part[((j * HI_TG + pg) * S + s) * HI_W + f] = h[j][s] * ko;
+    __syncthreads();
+    for (int c = t; c < NP * S; c += HI_THREADS) {
+      const int s = c % S, pp = c / S;
+      const int m = blockIdx.x * NP + pp;
+      if (m >= N || sp.out[s] < 0) continue;
+      const f32x4* r = reinterpret_cast<const f32x4*>(part + (size_t)c * HI_W);
+      f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+      for (int k = 0; k < HI_W / 4; ++k) a4 += r[k];
+      float a = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+      if (s == 0) a += Ko[wl * dout + q];
+      J[((size_t)sp.out[s] * ldJ + j0 + m) * dout + q] = a;
+    }
+    if (q + 1 < dout) __syncthreads();  // the next output's products overwrite part
+  }
+}
+
+// adjoint chain, NP points per workgroup (jet_hi_chain_kernel's layout; a thread sums the vector
+// partials of its PT points in point order before the group sum of hi_vsum) -> vslab row blockIdx.x
+template <int S, bool CH, bool X3, int NP>
+__global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
+jet_hi_chain_tile_kernel(int N, const float* __restrict__ P, NetDims d, HiSpec sp, const float* __restrict__ X,
+                         const float* __restrict__ dJ, int ldJ, int j0, const float* __restrict__ Zb,
+                         float* __restrict__ Bb, float* __restrict__ vslab) {
+  constexpr int PT = NP / HI_TG;
+  extern __shared__ __attribute__((aligned(16))) float hi_lds[];
+  const HiLdsT<NP> L = hi_lds_map_t<NP>(hi_lds, S, X3);
+  const int t = threadIdx.x, pg = t >> 7, f = t & (HI_W - 1);
+  const int Lh = d.n_hidden, dout = d.d_out, din = d.d_in, nvs = hi_nvs(d);
+  bool ok[PT];
+  int n[PT];
+#pragma unroll
+  for (int j = 0; j < PT; ++j) {
+    const int m = blockIdx.x * NP + j * HI_TG + pg;
+    ok[j] = m < N;
+    n[j] = ok[j] ? m : N - 1;
+  }
+  HiWRegs wr;
+  if (Lh > 1) hi_get_w(wr, P, d, Lh - 1);
+  const int wl = hw(d, Lh - 1);
+  const float* Ko = P + off_layer(d, Lh);
+  float* vrow = vslab + (size_t)blockIdx.x * hi_vrow(d);
+  float hb[PT][S], z[PT][S];
+  float vo[TDQ_MAXO], vbo[TDQ_MAXO];  // Ko / bo partials of this thread's points
+  {
+    float ko[TDQ_MAXO];
+#pragma unroll
+    for (int q = 0; q < TDQ_MAXO; ++q) {
+      ko[q] = ldm(Ko + (f < wl ? f : wl - 1) * dout + (q < dout ? q : dout - 1), q < dout && f < wl);
+      vo[q] = 0.f;
+      vbo[q] = 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
+      float u[S][TDQ_MAXO];
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const int orow = sp.out[s] >= 0 ? sp.out[s] : 0;
+#pragma unroll
+        for (int q = 0; q < TDQ_MAXO; ++q)
+          u[s][q] = dJ[((size_t)orow * ldJ + j0 + n[j]) * dout + (q < dout ? q : 0)];
+        z[j][s] = Zb[hi_row(Lh - 1, n[j], s, S, N) + f];
+      }
+      __builtin_amdgcn_sched_barrier(0);  // the point's loads in flight before the first use
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+#pragma unroll
+        for (int q = 0; q < TDQ_MAXO; ++q) u[s][q] = (sp.out[s] >= 0 && ok[j] && q < dout) ? u[s][q] : 0.f;
+        z[j][s] = f < wl ? z[j][s] : 0.f;
+      }
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        float a = 0.f;
+#pragma unroll
+        for (int q = 0; q < TDQ_MAXO; ++q) a = fmaf(ko[q], u[s][q], a);
+        hb[j][s] = a;
+      }
+      float h[S];
+      hi_tanh_f<S, CH>(sp, z[j], h);
+#pragma unroll
+      for (int q = 0; q < TDQ_MAXO; ++q) {
+        float a = 0.f;
+#pragma unroll
+        for (int s = 0; s < S; ++s) a = fmaf(f < wl ? h[s] : 0.f, u[s][q], a);
+        vo[q] += a;
+        vbo[q] += u[0][q];
+      }
+    }
+  }
+  for (int i = Lh - 1; i >= 0; --i) {
+    const int wi = hw(d, i);
+    {
+      float vb = 0.f, vk[TDQ_MAXD];
+#pragma unroll
+      for (int v = 0; v < TDQ_MAXD; ++v) vk[v] = 0.f;
+#pragma unroll
+      for (int j = 0; j < PT; ++j) {
+        float zb[S];
+        if (f < wi) {
+          hi_tanh_b<S, CH>(sp, z[j], hb[j], zb);
+        } else {
+#pragma unroll
+          for (int s = 0; s < S; ++s) zb[s] = 0.f;
+        }
+        if (ok[j]) {
+#pragma unroll
+          for (int s = 0; s < S; ++s) Bb[hi_row(i, n[j], s, S, N) + f] = zb[s];
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) hi_put_a_t<X3, NP>(L, (j * HI_TG + pg) * S + s, f, zb[s]);
+        vb += ok[j] ? zb[0] : 0.f;
+        if (i == 0) {  // K0 partials: the input point (once per workgroup)
+#pragma unroll
+          for (int v = 0; v < TDQ_MAXD; ++v) {
+            const float xv = X[(size_t)n[j] * din + (v < din ? v : din - 1)];
+            float g = xv * zb[0];
+#pragma unroll
+            for (int s = 1; s < S; ++s) g += (sp.order[s] == 1 && sp.var[s] == v) ? zb[s] : 0.f;
+            vk[v] += ok[j] ? g : 0.f;
+          }
+        }
+      }
+      float* V = L.V + pg * nvs * HI_W;
+      V[f] = vb;
+      if (i == 0) {
+#pragma unroll
+        for (int v = 0; v < TDQ_MAXD; ++v)
+          if (v < din) V[(1 + v) * HI_W + f] = vk[v];
+      }
+      if (i == Lh - 1) {
+        const int vko = hi_vko(d);
+#pragma unroll
+        for (int q = 0; q < TDQ_MAXO; ++q) {
+          if (q >= dout) break;
+          V[(vko + q) * HI_W + f] = vo[q];
+          V[(vko + dout + q) * HI_W + f] = vbo[q];
+        }
+      }
+    }
+    if (i == 0) {
+      __syncthreads();
+      hi_vsum(L, vrow, d, i, pg, f);
+      break;
+    }
+    // hb_{i-1}[k] = sum_o zb_i[o] W_i[k][o]; the next pre-activations load meanwhile
+    hi_put_w(L, wr, d, i);
+    __syncthreads();
+    hi_vsum(L, vrow, d, i, pg, f);
+    if (i >= 2) hi_get_w(wr, P, d, i - 1);
+    const int wp = hw(d, i - 1);
+#pragma unroll
+    for (int j = 0; j < PT; ++j)
+#pragma unroll
+      for (int s = 0; s < S; ++s) z[j][s] = Zb[hi_row(i - 1, n[j], s, S, N) + f];  // used (masked) after the GEMM
+    __builtin_amdgcn_sched_barrier(0);
+    hi_mma_t<true, X3, NP, S>(L, wi);
+    __syncthreads();  // hb in R; GEMM reads of A / W done
+#pragma unroll
+    for (int j = 0; j < PT; ++j)
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const float r = L.R[((j * HI_TG + pg) * S + s) * HI_AS + f];
+        hb[j][s] = f < wp ? r : 0.f;
+        z[j][s] = f < wp ? z[j][s] : 0.f;
+      }
+    __syncthreads();  // R, A, V reused by the next layer
+  }
+}
+
 namespace {
 
 // spec_i: [S, order[S], var[S], out[S], n_terms, (stream, k, nb, b0, b1, b2, b3) x n_terms]
@@ -1026,6 +1411,87 @@ int hi_wgrad(int N, const NetDims& d, const HiSpec& sp, const float* Hb, const f
 // one activation-sized scratch buffer (Z, H or B), in floats
 size_t hi_act_floats(int N, int n_hidden) { return (size_t)n_hidden * N * HI_MAXS * HI_W; }
 
+// ---- tile entry points (large point sets): tile = points per workgroup, 4 (the kernels above) | 8 | 16
+// weight-gradient splits grow with the point count (one slab row each; a split of 256 points is a
+// handful of staging batches), up to HI_KS_MAX rows for the serial sum of hi_tile_reduce
+constexpr int HI_KS_MAX = 64;
+constexpr int HI_T_NMAX = 1 << 27;  // N S and the workgroup counts stay in int
+int hi_t_splits(int N) { return std::min(HI_KS_MAX, std::max(1, (N + 255) / 256)); }
+size_t hi_t_act_floats(int N, int n_hidden, int S) { return (size_t)n_hidden * N * S * HI_W; }
+bool hi_t_fits(int tile, int S, const NetDims& d, bool chain) {
+  if (tile == HI_NP) return hi_lds_fits(S, d);
+  if (tile != 8 && tile != 16) return false;
+  if (tile * S > HI_W) return false;
+  return hi_t_lds_floats(tile, S, chain ? hi_nvs(d) : 0, hi_x3(d.n_hidden)) * sizeof(float) <= HI_LDS_MAX;
+}
+// instantiations no network can launch (LDS at the smallest V area, hi_nvs >= 3) are left out
+constexpr bool hi_t_any(int NP, int S, bool x3, int nvs) {
+  return NP * S <= HI_W && hi_t_lds_floats(NP, S, nvs, x3) * sizeof(float) <= HI_LDS_MAX;
+}
+
+template <int S, bool CH, bool X3, int NP>
+int hi_launch_fwd_t(const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp, float* J, int ldJ,
+                    int j0, float* Zb, float* Hb, hipStream_t st) {
+  if constexpr (!hi_t_any(NP, S, X3, 0)) {
+    return (int)hipErrorInvalidValue;
+  } else {
+    static bool attr = false;
+    if (!attr) {
+      hi_attr(&jet_hi_fwd_tile_kernel<S, CH, X3, NP>);
+      attr = true;
+    }
+    hipLaunchKernelGGL((jet_hi_fwd_tile_kernel<S, CH, X3, NP>), dim3((N + NP - 1) / NP), dim3(HI_THREADS),
+                       hi_t_lds_floats(NP, S, 0, X3) * sizeof(float), st, X, N, P, d, sp, J, ldJ, j0, Zb, Hb);
+    TDQ_CHECK_LAUNCH();
+    return 0;
+  }
+}
+
+template <int S, bool CH, bool X3, int NP>
+int hi_launch_chain_t(int N, const float* P, const NetDims& d, const HiSpec& sp, const float* X, const float* dJ,
+                      int ldJ, int j0, const float* Zb, float* Bb, float* vslab, hipStream_t st) {
+  if constexpr (!hi_t_any(NP, S, X3, 3)) {
+    return (int)hipErrorInvalidValue;
+  } else {
+    static bool attr = false;
+    if (!attr) {
+      hi_attr(&jet_hi_chain_tile_kernel<S, CH, X3, NP>);
+      attr = true;
+    }
+    hipLaunchKernelGGL((jet_hi_chain_tile_kernel<S, CH, X3, NP>), dim3((N + NP - 1) / NP), dim3(HI_THREADS),
+                       hi_t_lds_floats(NP, S, hi_nvs(d), X3) * sizeof(float), st, N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb,
+                       vslab);
+    TDQ_CHECK_LAUNCH();
+    return 0;
+  }
+}
+
+template <int NP>
+int hi_fwd_t(const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp, float* J, int ldJ, int j0,
+             float* Zb, float* Hb, hipStream_t st) {
+  const bool ch = sp.chain != 0, x3 = hi_x3(d.n_hidden);
+#define HI_F(SS, CC)                                                                                  \
+  if (sp.S == SS && ch == CC)                                                                         \
+    return x3 ? hi_launch_fwd_t<SS, CC, true, NP>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st)             \
+              : hi_launch_fwd_t<SS, CC, false, NP>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st);
+  HI_CASES(HI_F)
+#undef HI_F
+  return (int)hipErrorInvalidValue;
+}
+
+template <int NP>
+int hi_chain_t(int N, const float* P, const NetDims& d, const HiSpec& sp, const float* X, const float* dJ, int ldJ,
+               int j0, const float* Zb, float* Bb, float* vslab, hipStream_t st) {
+  const bool ch = sp.chain != 0, x3 = hi_x3(d.n_hidden);
+#define HI_B(SS, CC)                                                                                  \
+  if (sp.S == SS && ch == CC)                                                                         \
+    return x3 ? hi_launch_chain_t<SS, CC, true, NP>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st)   \
+              : hi_launch_chain_t<SS, CC, false, NP>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st);
+  HI_CASES(HI_B)
+#undef HI_B
+  return (int)hipErrorInvalidValue;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1101,6 +1567,84 @@ int tdq_jet_hi_lds_ok(int S, int d_in, int d_out, int n_hidden) {
   d.d_out = d_out;
   d.n_hidden = n_hidden;
   return S >= 1 && S <= HI_MAXS && d_in <= TDQ_MAXD && d_out <= TDQ_MAXO && hi_lds_fits(S, d) ? 1 : 0;
+}
+
+// ---- tile entry points: `tile` points per workgroup (4: the kernels of the entry points above; 8 |
+// 16: the tile kernels), scratch sized by the plan's S, weight-gradient splits growing with N
+
+// whether `tile` serves S streams on this geometry: chain = 0 the forward, 1 the adjoint chain
+int tdq_jet_hi_tile_ok(int tile, int S, int d_in, int d_out, int n_hidden, int chain) {
+  NetDims d;
+  d.d_in = d_in;
+  d.d_out = d_out;
+  d.n_hidden = n_hidden;
+  return S >= 1 && S <= HI_MAXS && d_in >= 1 && d_in <= TDQ_MAXD && d_out >= 1 && d_out <= TDQ_MAXO && n_hidden >= 1 &&
+                 hi_t_fits(tile, S, d, chain != 0)
+             ? 1
+             : 0;
+}
+
+// Z | H | B of S streams, in floats (-1: outside the limits)
+int64_t tdq_jet_hi_tile_scratch_floats(int N, int n_hidden, int S) {
+  if (N < 0 || N > HI_T_NMAX || n_hidden < 1 || n_hidden > TDQ_MAXL || S < 1 || S > HI_MAXS) return -1;
+  return 3 * (int64_t)hi_t_act_floats(N, n_hidden, S);
+}
+
+// tile slab (hi_t_splits rows) + the vector slab (one row per workgroup of the chain's tile), in floats
+int64_t tdq_jet_hi_tile_work_floats(int N, int d_in, const int* widths, int d_out, int n_hidden, int tile) {
+  NetDims d;
+  if (!hi_dims(d, d_in, widths, d_out, n_hidden) || N < 0 || N > HI_T_NMAX) return -1;
+  if (tile != 4 && tile != 8 && tile != 16) return -1;
+  const int64_t nwg = ((int64_t)N + tile - 1) / tile;
+  return (int64_t)hi_t_splits(N) * slab_stride(param_count(d)) + nwg * hi_vrow(d);
+}
+
+int tdq_jet_hi_tile_fwd(const float* X, int N, const float* P, int d_in, const int* widths, int d_out, int n_hidden,
+                        const int* spec_i, const float* spec_c, float* J, int ldJ, int j0, float* Z, int tile,
+                        void* stream) {
+  NetDims d;
+  HiSpec sp;
+  if (!hi_dims(d, d_in, widths, d_out, n_hidden) || !hi_spec(sp, spec_i, spec_c) || !hi_t_fits(tile, sp.S, d, false) ||
+      N > HI_T_NMAX)
+    return (int)hipErrorInvalidValue;
+  if (N <= 0) return 0;
+  const size_t A = hi_t_act_floats(N, n_hidden, sp.S);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (tile == 8) return hi_fwd_t<8>(X, N, P, d, sp, J, ldJ, j0, Z, Z + A, st);
+  if (tile == 16) return hi_fwd_t<16>(X, N, P, d, sp, J, ldJ, j0, Z, Z + A, st);
+  return hi_fwd(X, N, P, d, sp, J, ldJ, j0, Z, Z + A, st);
+}
+
+// part as in tdq_jet_hi_bwd_part; `tile` is the chain's (the vector slab's row count follows it)
+int tdq_jet_hi_tile_bwd_part(const float* X, int N, const float* P, int d_in, const int* widths, int d_out,
+                             int n_hidden, const int* spec_i, const float* spec_c, const float* dJ, int ldJ, int j0,
+                             float* Z, float* work, float* grad, int part, int tile, void* stream) {
+  NetDims d;
+  HiSpec sp;
+  if (!hi_dims(d, d_in, widths, d_out, n_hidden) || !hi_spec(sp, spec_i, spec_c) || !hi_t_fits(tile, sp.S, d, true) ||
+      N > HI_T_NMAX || part < 0 || part > 2)
+    return (int)hipErrorInvalidValue;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int Ptot = param_count(d), Pst = slab_stride(Ptot);
+  if (N <= 0) return (int)hipMemsetAsync(grad, 0, sizeof(float) * Ptot, st);
+  const size_t A = hi_t_act_floats(N, n_hidden, sp.S);
+  const int ks = hi_t_splits(N), nwg = (N + tile - 1) / tile;
+  float* vslab = work + (size_t)ks * Pst;
+  if (part != 2) {
+    const int rc = tile == 8    ? hi_chain_t<8>(N, P, d, sp, X, dJ, ldJ, j0, Z, Z + 2 * A, vslab, st)
+                   : tile == 16 ? hi_chain_t<16>(N, P, d, sp, X, dJ, ldJ, j0, Z, Z + 2 * A, vslab, st)
+                                : hi_chain(N, P, d, sp, X, dJ, ldJ, j0, Z, Z + 2 * A, vslab, st);
+    if (rc || part == 1) return rc;
+  }
+  const int rc = hi_wgrad(N, d, sp, Z + A, Z + 2 * A, work, Pst, ks, st);
+  if (rc) return rc;
+  const int ntile = off_layer(d, n_hidden) - off_layer(d, 1);
+  const int ntb = (ntile + 255) / 256;
+  const int ncol = (n_hidden + d_in) * HI_W + HI_W * TDQ_MAXO + TDQ_MAXO;
+  hipLaunchKernelGGL(jet_hi_reduce_kernel, dim3(ntb + (ncol + 3) / 4), dim3(256), 0, st, work, ks, Pst, vslab, nwg,
+                     hi_vrow(d), ntb, d, grad);
+  TDQ_CHECK_LAUNCH();
+  return 0;
 }
 
 int tdq_jet_hi_limits(int* out) {

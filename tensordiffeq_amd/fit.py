@@ -613,6 +613,10 @@ def point_ranges(program, fop):
             b = None
         if b is None:
             return None
+        if not cuts[1:] and a < getattr(program, "n_hi", 0) and getattr(program, "hi_op", None) is not None:
+            # the first range runs the high-order kernels over [0, n_hi): a cut inside that block (a
+            # KdV-type residual, whose high-order points are most of the set) means one range
+            return None
         cuts.append(a)
         blks.append(b)
     cuts.append(N)

@@ -179,7 +179,13 @@ class LossProgram:
                     ok_lo, why_lo = jet_mlp.hip_eligible(self.net, JetPlan(lo_req, self.d_in), self.device)
                     n_hi = sum(self.segments[i].n for i in hi)
                     n_lo = sum(sg.n for sg in self.segments) - n_hi
-                    if ok_lo and n_lo >= n_hi:
+                    # a high-order set larger than the rest (a KdV-type residual: the whole collocation
+                    # set) is worth the split only on the high-order kernels, within their scratch cap
+                    if ok_lo and n_lo < n_hi:
+                        ok_lo, why_hi = self._hi_large_ok(JetPlan(hi_req, self.d_in), n_hi)
+                        if not ok_lo:
+                            reasons.append(why_hi)
+                    if ok_lo:
                         for i in hi:
                             self.segments[i].hi = True
                         self.plan = JetPlan(lo_req, self.d_in)
@@ -426,7 +432,9 @@ class LossProgram:
             from ..ops.jet_hi import HiJetOp
             idx, _ = self.fused_streams()
             extra = {m: idx[m] for m in self.plan_hi.streams if m not in self.plan.index}
-            self.hi_op = HiJetOp(self.net, self.plan_hi, extra, self.X_all, self.n_hi, self.device)
+            tile = os.environ.get("TDQ_HI_TILE", "auto").strip().lower()
+            self.hi_op = HiJetOp(self.net, self.plan_hi, extra, self.X_all, self.n_hi, self.device,
+                                 tile=None if tile in ("auto", "") else int(tile))
         return True
 
     def fused_streams(self):
@@ -439,6 +447,20 @@ class LossProgram:
                 if m not in idx:
                     idx[m] = len(idx)
         return idx, len(idx)
+
+    def _hi_large_ok(self, plan_hi, n_hi):
+        """Whether a high-order point set larger than the rest of the program goes mixed: the plan
+        within the high-order kernels' envelope and their activation scratch under the byte cap
+        (``TDQ_HI_SCRATCH_BYTES``, ops/jet_hi.py)."""
+        from ..ops import jet_hi
+        ok, why = jet_hi.eligible(self.net, plan_hi)
+        if not ok:
+            return False, f"order-{plan_hi.order} segments outside the high-order kernels: {why}"
+        need, cap = jet_hi.scratch_bytes(n_hi, len(self.net.layer_sizes) - 2, plan_hi.S), jet_hi.scratch_cap()
+        if need > cap:
+            return False, (f"high-order scratch of {n_hi} points x {plan_hi.S} streams needs {need} bytes, above the "
+                           f"cap of {cap} (TDQ_HI_SCRATCH_BYTES)")
+        return True, ""
 
     def _hi_kernels_ok(self):
         """Mixed mode on the fused path: the main plan on the split-bf16 kernels and the high-order

@@ -95,6 +95,12 @@ def _declare(lib):
         "tdq_jet_hi_bwd_part": (I, [P, I, P, I, P, I, I, P, P, P, I, I, P, P, P, I, P]),
         "tdq_jet_hi_limits": (I, [P]),
         "tdq_jet_hi_lds_ok": (I, [I, I, I, I]),
+        # the same for large point sets: 4 / 8 / 16 points per workgroup, scratch sized by S
+        "tdq_jet_hi_tile_ok": (I, [I, I, I, I, I, I]),
+        "tdq_jet_hi_tile_scratch_floats": (L, [I, I, I]),
+        "tdq_jet_hi_tile_work_floats": (L, [I, I, P, I, I, I]),
+        "tdq_jet_hi_tile_fwd": (I, [P, I, P, I, P, I, I, P, P, P, I, I, P, I, P]),
+        "tdq_jet_hi_tile_bwd_part": (I, [P, I, P, I, P, I, I, P, P, P, I, I, P, P, P, I, I, P]),
         # one-shot peer-memory all-reduce (csrc/peer.hip, parallel/peer.py)
         "tdq_peer_maxw": (I, []),
         "tdq_peer_chunk": (I, []),
