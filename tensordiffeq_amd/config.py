@@ -28,6 +28,11 @@ dp_graph               TDQ_DP_GRAPH=0 disables     RCCL all-reduce captured insi
 nan_check              TDQ_NAN_CHECK=0 disables    device loss-history NaN/Inf scan (fit.py)
 (fused_step)           TDQ_FUSED_STEP=0 disables   one-launch forward -> loss -> backward (bf16 Adam
                                                    step, bf16x3 L-BFGS objective; ops/fused_step.py)
+(tail_one)             TDQ_TAIL_ONE=0 disables     one-launch step tail after the fused step (a workgroup
+                                                   owns 256 theta columns from the slab rows to Adam;
+                                                   0: the two launches) and the one-launch slab
+                                                   reduction of the L-BFGS objective / DP step (bf16
+                                                   slab rows; fp32 rows always take two passes)
 (split)                TDQ_SPLIT                   auto (cut at 0.38 for bf16, 0.35 for bf16x3) | off | cut
                                                    fraction: two point ranges on concurrent graph
                                                    branches (fit.point_ranges)

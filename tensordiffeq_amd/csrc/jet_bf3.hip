@@ -13,8 +13,29 @@
 //                 weights snapshot, and the next step's weight images: every updated weight is
 //                 scattered straight into its forward / backward A-image (bf16 hi + lo) or aux
 //                 slot, so the next forward runs without a pack launch.
+// After the one-launch fused step (jet_fused.h) the same work is ONE launch (tdq_step_tail1_bf3,
+// tail_one_kernel below): a workgroup owns 256 theta columns from the slab rows to the updated
+// parameters, the first-pass partials stay in LDS, and no block waits for another - the half of
+// the bookkeeping that every Adam block needs (counters += 1, the best loss before the step) is
+// done ahead of the step by the fused launch (step_prebook), the rest each block derives from the
+// loss partials.  MI355X, 50k-point bf16 step: 10.7-11.2 us against 5.6-6.8 + 6.2-6.7 us; results
+// bit-identical.  tdq_fused_step itself became ~1 us slower with the pre-bookkeeping compiled in
+// (116.0-116.5 against 114.9-115.7 us, also when the pointer is null and nothing runs: the cost is
+// the kernel's changed code, not the chain of loads; profiles/r15_fused_step_cost.txt), so bench.py
+// gains +1.0-1.1 %, and the two-launch path (TDQ_TAIL_ONE=0, DP) is ~0.4 % slower than it was.
+// Steps without a fused launch, DP steps and
+// pre-reduced chunks (c_first > 0) keep the two launches.  The gradient-only callers
+// (tdq_dp_tail_a_bf3: DP step, L-BFGS objective) use the same column blocks up to grad
+// (tail_one_reduce_kernel) for bf16 slab rows, where that was measured faster.  The fp32-row
+// instantiations (tail_one_kernel<false>, tail_one_reduce_kernel<false>) are reached by the
+// kernel-level tests only: the engine's one-launch tail follows the bf16 fused step (bf16 rows), and
+// the fp32-row reduction showed no gain (tdq_dp_tail_a_bf3).
+#include <cstdlib>
+
 #include "jet_fused3.h"
 #include "optim_common.h"
+
+static_assert(FZ_MAX_COUNTERS == TDQ_MAX_COUNTERS, "FzPreBook holds every step counter");
 
 // A-operand images: img[layer-1][o][kb][hl][lane] = 8 bf16 (hl 0 = hi, 1 = lo)
 //   element j of lane (p, g): row 16o + p, k = 8g + j -> feature 32kb + (j<4 ? 4g+j : 16+4g+j-4)
@@ -101,6 +122,29 @@ struct TailBook {
   Counters cnt;
 };
 
+// The loss reduction + bookkeeping block of both tails: loss partials -> per-term losses / scalar
+// gradients (loss_slot_sum: the loss_reduce_kernel order; wave 0), then the bookkeeping on the
+// summed terms.  bump: the bookkeeping also increments the step counters.
+__device__ __forceinline__ void tail_book_block(const TailBook& tb, bool bump) {
+  if (threadIdx.x >= 64) return;
+  const int ns = tb.n_terms + tb.n_scal;
+  for (int slot = 0; slot < ns; ++slot) {
+    const float s = loss_slot_sum(tb.lpart, tb.n_lblocks, ns, slot, threadIdx.x);
+    if (threadIdx.x == 0) {
+      if (slot < tb.n_terms) tb.losses[slot] = s;
+      else tb.dscal[slot - tb.n_terms] = s;
+    }
+  }
+  if (threadIdx.x == 0 && tb.hist == nullptr && tb.total != nullptr) {  // loss + gradient only (L-BFGS)
+    float s = 0.f;
+    for (int t = 0; t < tb.n_terms; ++t) s += tb.losses[t];
+    *tb.total = s;
+  }
+  if (threadIdx.x == 0 && tb.hist != nullptr)  // DP: the bookkeeping waits for the all-reduce
+    step_book_body(tb.total, tb.losses, tb.n_terms, 1, tb.hist, tb.hist_rows, tb.epoch, tb.best_loss, tb.best_epoch,
+                   tb.improved, tb.cnt, bump);
+}
+
 // chunks [c0, c0 + gridDim.y) of the first pass; blocks x >= nqb (at most one, and only with
 // gridDim.x > nqb) run the loss reduction + bookkeeping
 __global__ void __launch_bounds__(256) tail_reduce1_kernel(const float* __restrict__ slab, float* __restrict__ part,
@@ -116,33 +160,7 @@ __global__ void __launch_bounds__(256) tail_reduce1_kernel(const float* __restri
     return;
   }
   if (blockIdx.y != 0) return;
-  // loss partials -> per-term losses / scalar gradients (the loss_reduce_kernel order), then the
-  // bookkeeping on the summed terms
-  __shared__ float sh[256];
-  const int ns = tb.n_terms + tb.n_scal;
-  for (int slot = 0; slot < ns; ++slot) {
-    float s = 0.f;
-    for (int b = threadIdx.x; b < tb.n_lblocks; b += 256) s += tb.lpart[(size_t)b * ns + slot];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-      if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      if (slot < tb.n_terms) tb.losses[slot] = sh[0];
-      else tb.dscal[slot - tb.n_terms] = sh[0];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && tb.hist == nullptr && tb.total != nullptr) {  // loss + gradient only (L-BFGS)
-    float s = 0.f;
-    for (int t = 0; t < tb.n_terms; ++t) s += tb.losses[t];
-    *tb.total = s;
-  }
-  if (threadIdx.x == 0 && tb.hist != nullptr)  // DP: the bookkeeping waits for the all-reduce
-    step_book_body(tb.total, tb.losses, tb.n_terms, 1, tb.hist, tb.hist_rows, tb.epoch, tb.best_loss, tb.best_epoch,
-                   tb.improved, tb.cnt);
+  tail_book_block(tb, true);
 }
 
 // gx (optional): a second gradient added element-wise (the high-order points' part, jet_hi.hip)
@@ -154,6 +172,19 @@ __global__ void __launch_bounds__(256) slab_reduce2_bf3(const float* __restrict_
 #pragma unroll
   for (int e = 0; e < 4; ++e)
     if (4 * q + e < P) grad[4 * q + e] = gx != nullptr ? a[e] + gx[4 * q + e] : a[e];
+}
+
+// One element of the Adam update of both tails: p / m / v as loaded, gradient g; theta (th) also
+// goes to the best-weights snapshot (before the update, do_snap) and into the weight images
+__device__ __forceinline__ void tail_adam_elem(const AdamGroup& gr, int64_t e, float p, float m, float v, float g,
+                                               float lr_t, bool th, bool do_snap, float* __restrict__ snap,
+                                               const TailImg& ti) {
+  if (do_snap && th) snap[e] = p;
+  adam_elem(p, gr.sign * g, m, v, gr.b1, gr.b2, gr.eps, lr_t);
+  gr.p[e] = p;
+  gr.m[e] = m;
+  gr.v[e] = v;
+  if (th && ti.fimg != nullptr) scatter_param(p, (int)e, ti);
 }
 
 // Adam over every group, one ELEMENT per thread (args.start in elements; float4 slots per thread
@@ -174,37 +205,141 @@ __global__ void __launch_bounds__(256) tail_adam_kernel(AdamArgs args, const flo
     const bool th = gi == 0;
     float g;
     if (th && part != nullptr) {
-      float a0 = 0.f, a1 = 0.f;
-      int c = 0;
-      for (; c + 7 < chunks; c += 8) {  // (slab_reduce2_sum's order, eight loads in flight)
-        float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = part[(size_t)(c + k) * Pst + e];
-#pragma unroll
-        for (int k = 0; k < 8; k += 2) {
-          a0 += v[k];
-          a1 += v[k + 1];
-        }
-      }
-      for (; c + 1 < chunks; c += 2) {
-        a0 += part[(size_t)c * Pst + e];
-        a1 += part[(size_t)(c + 1) * Pst + e];
-      }
-      if (c < chunks) a0 += part[(size_t)c * Pst + e];
-      g = a0 + a1;
+      g = slab_part_sum(part + e, (size_t)Pst, chunks);
       if (gx != nullptr) g += gx[e];
       const_cast<float*>(gr.g)[e] = g;
     } else {
       g = gr.g[e];
     }
-    float p = gr.p[e], m = gr.m[e], v = gr.v[e];
-    if (do_snap && th) snap[e] = p;
-    adam_elem(p, gr.sign * g, m, v, gr.b1, gr.b2, gr.eps, adam_lr_t(gr));
-    gr.p[e] = p;
-    gr.m[e] = m;
-    gr.v[e] = v;
-    if (th && ti.fimg != nullptr) scatter_param(p, (int)e, ti);
+    tail_adam_elem(gr, e, gr.p[e], gr.m[e], gr.v[e], g, adam_lr_t(gr), th, do_snap, snap, ti);
   }
+}
+
+// ---- the one-launch tail: column blocks --------------------------------------------------------
+// A block of 256 threads owns 256 consecutive theta columns from the slab rows through to the
+// updated parameter, so no block waits for another (no atomics, fences or counters):
+//   1. thread (column group, chunk) sums its chunk's rows of its columns in slab_chunk_sum8 /
+//      slab_chunk_sum's order (bf16 rows: 8 columns x 8 chunks, 16-byte loads; fp32 rows: float4
+//      columns x 4 chunks, twice) and leaves the fp32 partial in LDS as [chunk][column];
+//   2. after one barrier thread j sums column j's partials (slab_part_sum), adds gx, stores grad;
+//   3. (ADAM) the Adam update of the element, snapshot and weight images (tail_adam_elem).
+// Blocks [ncb, ncb + nob) (ADAM) update the other groups, one element per thread; the last block is
+// the loss reduction + bookkeeping (tail_book_block) - without the counter increments under ADAM.
+// What an Adam block needs of the bookkeeping it derives itself: the step counters were
+// incremented and best_prev = the best loss before this step was stored ahead of the step
+// (step_prebook), the loss sums come from the loss partials in the bookkeeping block's order
+// (loss_slot_sum, wave 2), so improved = total < best_prev and a gradient that points into dscal
+// are the bits the bookkeeping block writes; adam_lr_t once per group (wave 3).
+#define TAIL1_MAX_SLOTS 64
+#define TAIL1_CHUNKS 8
+
+template <bool H>
+__device__ __forceinline__ void tail_one_partials(const void* __restrict__ slab, float* __restrict__ sp, int nwg,
+                                                  int Pst, int chunks, int cb, int tid) {
+  if constexpr (H) {
+    const int cg = tid & 31, c = tid >> 5, q8 = cb * 32 + cg;
+    if (8 * q8 < Pst && c < chunks) {
+      f32x4 s_lo, s_hi;
+      slab_chunk_sum8(slab, nwg, Pst, chunks, q8, c, s_lo, s_hi);
+      f32x4* o = reinterpret_cast<f32x4*>(sp + c * 256 + 8 * cg);
+      o[0] = s_lo;
+      o[1] = s_hi;
+    }
+  } else {
+    const int cq = tid & 63, q = cb * 64 + cq;
+    if (4 * q < Pst)
+      for (int c = tid >> 6; c < chunks; c += 4)
+        *reinterpret_cast<f32x4*>(sp + c * 256 + 4 * cq) = slab_chunk_sum<false>(slab, nwg, Pst, chunks, q, c);
+  }
+}
+
+struct TailOne {
+  const void* slab;
+  int nwg, Pst, P, chunks;
+  int ncb;  // theta column blocks
+  float* grad;
+  const float* gx;
+};
+
+// gradient only: the column blocks stop after grad, the last block reduces the loss partials
+template <bool H>
+__global__ void __launch_bounds__(256) tail_one_reduce_kernel(TailOne t, TailBook tb) {
+  __shared__ __attribute__((aligned(16))) float sp[TAIL1_CHUNKS * 256];
+  const int cb = blockIdx.x, tid = threadIdx.x;
+  if (cb >= t.ncb) {
+    tail_book_block(tb, true);
+    return;
+  }
+  tail_one_partials<H>(t.slab, sp, t.nwg, t.Pst, t.chunks, cb, tid);
+  __syncthreads();
+  const int e = cb * 256 + tid;
+  if (e < t.P) {
+    const float g = slab_part_sum(sp + tid, (size_t)256, t.chunks);
+    t.grad[e] = t.gx != nullptr ? g + t.gx[e] : g;
+  }
+}
+
+template <bool H>
+__global__ void __launch_bounds__(256) tail_one_kernel(TailOne t, TailBook tb, AdamArgs args,
+                                                       const float* __restrict__ best_prev,
+                                                       float* __restrict__ snap, TailImg ti) {
+  __shared__ __attribute__((aligned(16))) float sp[TAIL1_CHUNKS * 256];
+  __shared__ float s_lr[TDQ_MAX_GROUPS];
+  __shared__ float s_ls[TAIL1_MAX_SLOTS];
+  __shared__ float s_total;
+  const int cb = blockIdx.x, tid = threadIdx.x;
+  const int nob = (int)gridDim.x - 1 - t.ncb;
+  if (cb >= t.ncb + nob) {
+    tail_book_block(tb, false);
+    return;
+  }
+  // this thread's element: theta column cb * 256 + tid, or element idx of the other groups
+  const bool th = cb < t.ncb;
+  int gi = 0;
+  int64_t e = (int64_t)cb * 256 + tid;
+  bool live = e < t.P;
+  if (!th) {
+    const int64_t idx = args.start[1] + (int64_t)(cb - t.ncb) * 256 + tid;
+    live = idx < args.start[args.ngroups];
+    gi = live ? adam_group_of(args, idx) : 0;
+    e = idx - args.start[gi];
+  }
+  const AdamGroup gr = args.grp[gi];
+  float p = 0.f, m = 0.f, v = 0.f;
+  if (live) {  // issued ahead of the slab loads
+    p = gr.p[e];
+    m = gr.m[e];
+    v = gr.v[e];
+  }
+  const int ns = tb.n_terms + tb.n_scal;
+  if (tid >= 192) {  // wave 3: the bias-corrected step sizes
+    if (tid - 192 < args.ngroups) s_lr[tid - 192] = adam_lr_t(args.grp[tid - 192]);
+  } else if (tid >= 128) {  // wave 2: the loss sums and the total, as tail_book_block / step_book_body
+    for (int slot = 0; slot < ns; ++slot) {
+      const float s = loss_slot_sum(tb.lpart, tb.n_lblocks, ns, slot, tid - 128);
+      if (tid == 128) s_ls[slot] = s;
+    }
+    if (tid == 128) {
+      float lv = 0.f;
+      for (int k = 0; k < tb.n_terms; ++k) lv += s_ls[k];
+      s_total = lv;
+    }
+  }
+  if (th) tail_one_partials<H>(t.slab, sp, t.nwg, t.Pst, t.chunks, cb, tid);
+  __syncthreads();
+  if (!live) return;
+  float g;
+  if (th) {
+    g = slab_part_sum(sp + tid, (size_t)256, t.chunks);
+    if (t.gx != nullptr) g += t.gx[e];
+    t.grad[e] = g;
+  } else if (tb.n_scal > 0 && gr.g >= tb.dscal && gr.g + gr.n <= tb.dscal + tb.n_scal) {
+    g = s_ls[tb.n_terms + (int)(gr.g - tb.dscal) + (int)e];  // (the bookkeeping block writes dscal in this launch)
+  } else {
+    g = gr.g[e];
+  }
+  const bool do_snap = snap != nullptr && s_total < *best_prev;  // NaN never improves
+  tail_adam_elem(gr, e, p, m, v, g, s_lr[gi], th, do_snap, snap, ti);
 }
 
 namespace {
@@ -242,6 +377,13 @@ bool bf3_ok(int WT, int S, int d_in, int d_out, int n_hidden) {
   // WT = 8, S = 8 kernels
   return (WT == 2 || WT == 4 || WT == 8 || (WT == 16 && S <= 4)) && S >= 1 && S <= TDQ_MAXS &&
          d_in <= TDQ_MAXD && d_out <= TDQ_MAXO && n_hidden >= 1;
+}
+
+// TDQ_TAIL_ONE=0: the two-pass slab reduction of tdq_dp_tail_a_bf3 also for bf16 slab rows (read at
+// every call: A/B runs); the two-launch step tail is chosen by the caller (fit.py)
+bool tail_one_enabled() {
+  const char* v = getenv("TDQ_TAIL_ONE");
+  return v == nullptr || v[0] != '0' || v[1] != '\0';
 }
 
 int dispatch(bool fwd, int WT, int S, int nso, const Bf3Args& a) {
@@ -422,11 +564,13 @@ int tdq_jet_bwd_bf3(const float* X, const float* P, const float* dJ, const float
 // backward's gradient slabs (tdq_jet_bwd_bf3_ex with reduce = 0); grad: receives the reduced theta
 // gradient; scratch: the forward's scratch whose images are rewritten for the next step (nullptr:
 // leave them).  groups[0] must be theta (n == parameter count); its g pointer is replaced by grad.
-int tdq_step_tail_bf3(float* work, float* grad, float* scratch, int N, int d_in, const int* widths, int d_out, int n_hidden,
-                      int S, int lo, const float* lpart, int n_lblocks, int n_terms, int n_scal, float* losses,
-                      float* total, float* dscal, float* hist, int64_t hist_rows, int64_t* epoch, float* best_loss,
-                      int64_t* best_epoch, int* improved, double* const* counters, int ncnt, const void* groups,
-                      int ngroups, float* snap, int c_first, const float* gx, int rows, void* stream) {
+// best_prev = nullptr: the two launches; else the one-launch tail (tdq_step_tail1_bf3)
+static int step_tail_launch(float* work, float* grad, float* scratch, int N, int d_in, const int* widths, int d_out,
+                            int n_hidden, int S, int lo, const float* lpart, int n_lblocks, int n_terms, int n_scal,
+                            float* losses, float* total, float* dscal, float* hist, int64_t hist_rows, int64_t* epoch,
+                            float* best_loss, int64_t* best_epoch, int* improved, double* const* counters, int ncnt,
+                            const void* groups, int ngroups, float* snap, int c_first, const float* gx, int rows,
+                            const float* best_prev, void* stream) {
   NetDims d;
   if (!make_dims(d, d_in, widths, 0, d_out, n_hidden)) return (int)hipErrorInvalidValue;
   const int WT = width_tiles(d.width);
@@ -462,10 +606,6 @@ int tdq_step_tail_bf3(float* work, float* grad, float* scratch, int N, int d_in,
   for (int i = 0; i < TDQ_MAX_COUNTERS; ++i) tb.cnt.c[i] = i < ncnt ? counters[i] : nullptr;
   const int half = (int)slab_half(lo != 0);
   const int nqb = (Pst / (half ? 8 : 4) + 255) / 256;
-  // chunks [0, c_first) were pre-reduced (tdq_slab_prereduce_bf3) while the other range ran
-  hipLaunchKernelGGL(tail_reduce1_kernel, dim3(nqb + 1, chunks - c_first), dim3(256), 0, st, work, part, nwg_b, Pst,
-                     chunks, nqb, half, c_first, tb);
-  TDQ_CHECK_LAUNCH();
   TailImg ti{nullptr, nullptr, nullptr, d, WT};
   if (scratch != nullptr) {
     float *img, *bimg, *aux;
@@ -475,6 +615,24 @@ int tdq_step_tail_bf3(float* work, float* grad, float* scratch, int N, int d_in,
     ti.aux = aux;
   }
   const int64_t tot = args.start[ngroups];
+  if (best_prev != nullptr) {  // one launch: column blocks, the other groups' blocks, the bookkeeping block
+    const int64_t nob = (tot - args.start[1] + 255) / 256;
+    if (c_first != 0 || chunks > TAIL1_CHUNKS || n_terms + n_scal > TAIL1_MAX_SLOTS || hist == nullptr ||
+        nob > (1 << 30))
+      return (int)hipErrorInvalidValue;
+    const TailOne t{work, nwg_b, Pst, Ptot, chunks, (Pst + 255) / 256, grad, gx};
+    const dim3 grid((unsigned)(t.ncb + nob + 1));
+    if (half)
+      hipLaunchKernelGGL(tail_one_kernel<true>, grid, dim3(256), 0, st, t, tb, args, best_prev, snap, ti);
+    else
+      hipLaunchKernelGGL(tail_one_kernel<false>, grid, dim3(256), 0, st, t, tb, args, best_prev, snap, ti);
+    TDQ_CHECK_LAUNCH();
+    return 0;
+  }
+  // chunks [0, c_first) were pre-reduced (tdq_slab_prereduce_bf3) while the other range ran
+  hipLaunchKernelGGL(tail_reduce1_kernel, dim3(nqb + 1, chunks - c_first), dim3(256), 0, st, work, part, nwg_b, Pst,
+                     chunks, nqb, half, c_first, tb);
+  TDQ_CHECK_LAUNCH();
   int64_t blocks = (tot + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
@@ -483,6 +641,43 @@ int tdq_step_tail_bf3(float* work, float* grad, float* scratch, int N, int d_in,
   TDQ_CHECK_LAUNCH();
   return 0;
 }
+
+int tdq_step_tail_bf3(float* work, float* grad, float* scratch, int N, int d_in, const int* widths, int d_out, int n_hidden,
+                      int S, int lo, const float* lpart, int n_lblocks, int n_terms, int n_scal, float* losses,
+                      float* total, float* dscal, float* hist, int64_t hist_rows, int64_t* epoch, float* best_loss,
+                      int64_t* best_epoch, int* improved, double* const* counters, int ncnt, const void* groups,
+                      int ngroups, float* snap, int c_first, const float* gx, int rows, void* stream) {
+  return step_tail_launch(work, grad, scratch, N, d_in, widths, d_out, n_hidden, S, lo, lpart, n_lblocks, n_terms,
+                          n_scal, losses, total, dscal, hist, hist_rows, epoch, best_loss, best_epoch, improved,
+                          counters, ncnt, groups, ngroups, snap, c_first, gx, rows, nullptr, stream);
+}
+
+// The same end of a step in ONE launch (tail_one_kernel; c_first = 0, at most 8 first-pass chunks,
+// at most 64 loss slots - else an error).  The step's pre-bookkeeping must have run since the
+// previous tail: the counters already incremented, best_prev = best_loss (the fused launch given
+// an FzPreBook, or tdq_step_prebook).  Bit-identical to tdq_step_tail_bf3.
+int tdq_step_tail1_bf3(float* work, float* grad, float* scratch, int N, int d_in, const int* widths, int d_out,
+                       int n_hidden, int S, int lo, const float* lpart, int n_lblocks, int n_terms, int n_scal,
+                       float* losses, float* total, float* dscal, float* hist, int64_t hist_rows, int64_t* epoch,
+                       float* best_loss, int64_t* best_epoch, int* improved, double* const* counters, int ncnt,
+                       const void* groups, int ngroups, float* snap, int c_first, const float* gx, int rows,
+                       const float* best_prev, void* stream) {
+  if (best_prev == nullptr) return (int)hipErrorInvalidValue;
+  return step_tail_launch(work, grad, scratch, N, d_in, widths, d_out, n_hidden, S, lo, lpart, n_lblocks, n_terms,
+                          n_scal, losses, total, dscal, hist, hist_rows, epoch, best_loss, best_epoch, improved,
+                          counters, ncnt, groups, ngroups, snap, c_first, gx, rows, best_prev, stream);
+}
+
+// The pre-bookkeeping alone (one thread): pre = device pointer to an FzPreBook
+__global__ void step_prebook_kernel(const FzPreBook* __restrict__ pre) { step_prebook(pre); }
+int tdq_step_prebook(const void* pre, void* stream) {
+  if (pre == nullptr) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(step_prebook_kernel, dim3(1), dim3(1), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const FzPreBook*>(pre));
+  TDQ_CHECK_LAUNCH();
+  return 0;
+}
+int tdq_prebook_size() { return (int)sizeof(FzPreBook); }
 
 // Data-parallel step, first half (before the all-reduce): slab pass 1 + the loss reduction in one
 // launch (no bookkeeping: it needs the all-reduced terms), then slab pass 2 into grad (+ gx, the
@@ -510,8 +705,21 @@ int tdq_dp_tail_a_bf3(float* work, float* grad, int N, int d_in, const int* widt
   tb.losses = losses;
   tb.dscal = dscal;
   tb.total = total;
-  const int half = half_ovr >= 0 ? (half_ovr != 0) : (int)slab_half(lo != 0);
+  // half_ovr: -1 = the row type of `lo`; 0 / 1 = fp32 / bf16 rows; 2 (tests only) = fp32 rows reduced
+  // in ONE launch.  One launch is the default for bf16 rows only: 131.4-131.8 against 132.5-133.6 us
+  // per bf16 objective evaluation (slowest new 0.7 us ahead of the fastest parent run); with fp32 rows
+  // (the bf16x3 L-BFGS objective) 273.9-274.3 against 273.9-274.6 us, no gain
+  // (profiles/r15_lbfgs_reduce_one_ab.jsonl) - those keep the two passes.
+  const int half = half_ovr >= 0 ? (half_ovr == 1) : (int)slab_half(lo != 0);
+  const bool one = half ? tail_one_enabled() : half_ovr == 2;
   const int nqb = (Pst / (half ? 8 : 4) + 255) / 256, nq2 = (Pst / 4 + 255) / 256;
+  if (c_first == 0 && chunks <= TAIL1_CHUNKS && one) {  // both passes in one launch
+    const TailOne t{work, nwg_b, Pst, Ptot, chunks, (Pst + 255) / 256, grad, gx};
+    if (half) hipLaunchKernelGGL(tail_one_reduce_kernel<true>, dim3(t.ncb + 1), dim3(256), 0, st, t, tb);
+    else hipLaunchKernelGGL(tail_one_reduce_kernel<false>, dim3(t.ncb + 1), dim3(256), 0, st, t, tb);
+    TDQ_CHECK_LAUNCH();
+    return 0;
+  }
   hipLaunchKernelGGL(tail_reduce1_kernel, dim3(nqb + 1, chunks - c_first), dim3(256), 0, st, work, part, nwg_b, Pst,
                      chunks, nqb, half, c_first, tb);
   TDQ_CHECK_LAUNCH();
@@ -597,8 +805,10 @@ int tdq_dp_tail_b_bf3(float* scratch, int N, int d_in, const int* widths, int d_
 // from row 0, loss-partial rows prow.. (nacc floats each)
 int tdq_fused_step_launch(void* func, const float* X, float* scratch, float* work, int N, int d_in, const int* widths,
                           int d_out, int n_hidden, int S, const int* spec, int G, const void* lptrs,
-                          float* lpart, int prow, int nacc, int lo, void* stream) {
-  if (func == nullptr || N <= 0 || G < 1 || prow < 0 || nacc < 1 || lo < 0 || lo > 1)
+                          float* lpart, int prow, int nacc, int lo, const void* pre, void* stream) {
+  // pre (device FzPreBook, bf16 step only): the pre-bookkeeping of a step that ends in
+  // tdq_step_tail1_bf3; nullptr for every other caller
+  if (func == nullptr || N <= 0 || G < 1 || prow < 0 || nacc < 1 || lo < 0 || lo > 1 || (lo && pre != nullptr))
     return (int)hipErrorInvalidValue;
   NetDims d;
   if (!make_dims(d, d_in, widths, 0, d_out, n_hidden)) return (int)hipErrorInvalidValue;
@@ -627,6 +837,7 @@ int tdq_fused_step_launch(void* func, const float* X, float* scratch, float* wor
   P.lpart = lpart;
   P.prow = prow;
   P.nacc = nacc;
+  P.pre = reinterpret_cast<const FzPreBook*>(pre);
   void* args[] = {(void*)&P};
   return (int)hipModuleLaunchKernel((hipFunction_t)func, (unsigned)G, 1, 1, 64 * FZ_WAVES, 1, 1, 0,
                                     reinterpret_cast<hipStream_t>(stream), args, nullptr);

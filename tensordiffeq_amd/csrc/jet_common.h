@@ -163,11 +163,12 @@ __device__ __forceinline__ f32x4 slab_ld4(const void* __restrict__ slab, size_t 
 
 // first reduction pass, float4 column q of chunk c: part[c][q] = sum of slab rows of the chunk
 // (fp32 partials; H: bf16 slab rows)
+// (slab_chunk_sum: the sum itself, shared with the column-block tail of jet_bf3.hip, which keeps
+// the partials in LDS)
 template <bool H = false>
-__device__ __forceinline__ void slab_reduce1_body(const void* __restrict__ slab, float* __restrict__ part, int nwg,
-                                                  int Pst, int chunks, int q, int c) {
+__device__ __forceinline__ f32x4 slab_chunk_sum(const void* __restrict__ slab, int nwg, int Pst, int chunks, int q,
+                                                int c) {
   const int lo = slab_chunk_lo(nwg, chunks, c), hi = slab_chunk_lo(nwg, chunks, c + 1);
-  const size_t row = (size_t)(Pst >> 2);
   f32x4 a0 = zero4(), a1 = zero4(), a2 = zero4(), a3 = zero4();
   int wgi = lo;
   for (; wgi + 3 < hi; wgi += 4) {
@@ -177,7 +178,12 @@ __device__ __forceinline__ void slab_reduce1_body(const void* __restrict__ slab,
     a3 += slab_ld4<H>(slab, wgi + 3, Pst, q);
   }
   for (; wgi < hi; ++wgi) a0 += slab_ld4<H>(slab, wgi, Pst, q);
-  reinterpret_cast<f32x4*>(part)[(size_t)c * row + q] = (a0 + a1) + (a2 + a3);
+  return (a0 + a1) + (a2 + a3);
+}
+template <bool H = false>
+__device__ __forceinline__ void slab_reduce1_body(const void* __restrict__ slab, float* __restrict__ part, int nwg,
+                                                  int Pst, int chunks, int q, int c) {
+  reinterpret_cast<f32x4*>(part)[(size_t)c * (size_t)(Pst >> 2) + q] = slab_chunk_sum<H>(slab, nwg, Pst, chunks, q, c);
 }
 
 // the same first pass over bf16 slab rows with 16-byte loads: 8 columns (float4 columns 2 q8 and
@@ -190,8 +196,9 @@ __device__ __forceinline__ void bf8_add(f32x4& lo, f32x4& hi, const uint4 u) {
   hi += f32x4{__uint_as_float(u.z << 16), __uint_as_float(u.z & 0xffff0000u), __uint_as_float(u.w << 16),
               __uint_as_float(u.w & 0xffff0000u)};
 }
-__device__ __forceinline__ void slab_reduce1_body8(const void* __restrict__ slab, float* __restrict__ part, int nwg,
-                                                   int Pst, int chunks, int q8, int c) {
+// (slab_chunk_sum8: the sums of float4 columns 2 q8 -> s_lo and 2 q8 + 1 -> s_hi)
+__device__ __forceinline__ void slab_chunk_sum8(const void* __restrict__ slab, int nwg, int Pst, int chunks, int q8,
+                                                int c, f32x4& s_lo, f32x4& s_hi) {
   const int lo = slab_chunk_lo(nwg, chunks, c), hi = slab_chunk_lo(nwg, chunks, c + 1);
   const uint4* s8 = reinterpret_cast<const uint4*>(slab) + q8;  // row stride Pst / 8 uint4
   const size_t rs = (size_t)(Pst >> 3);
@@ -220,22 +227,26 @@ __device__ __forceinline__ void slab_reduce1_body8(const void* __restrict__ slab
     bf8_add(a3, b3, u3);
   }
   for (; w < hi; ++w) bf8_add(a0, b0, s8[(size_t)w * rs]);
+  s_lo = (a0 + a1) + (a2 + a3);
+  s_hi = (b0 + b1) + (b2 + b3);
+}
+__device__ __forceinline__ void slab_reduce1_body8(const void* __restrict__ slab, float* __restrict__ part, int nwg,
+                                                   int Pst, int chunks, int q8, int c) {
   f32x4* p4 = reinterpret_cast<f32x4*>(part) + (size_t)c * (size_t)(Pst >> 2) + 2 * q8;
-  p4[0] = (a0 + a1) + (a2 + a3);
-  p4[1] = (b0 + b1) + (b2 + b3);
+  slab_chunk_sum8(slab, nwg, Pst, chunks, q8, c, p4[0], p4[1]);
 }
 
-// second pass: the gradient of float4 column q (fixed summation order: deterministic; chunk pairs
-// alternate between two accumulators, eight partials loaded before they are added)
-__device__ __forceinline__ f32x4 slab_reduce2_sum(const float* __restrict__ part, int Pst, int chunks, int q) {
-  const f32x4* p4 = reinterpret_cast<const f32x4*>(part) + q;
-  const size_t row = (size_t)(Pst >> 2);
-  f32x4 a0 = zero4(), a1 = zero4();
+// second pass: the sum of one column's chunk partials p[c * stride], c < chunks, as a float (one
+// column) or an f32x4 (a float4 column) - fixed summation order: deterministic; chunk pairs
+// alternate between two accumulators, eight partials loaded before they are added
+template <class T>
+__device__ __forceinline__ T slab_part_sum(const T* __restrict__ p, size_t stride, int chunks) {
+  T a0 = T{}, a1 = T{};
   int c = 0;
   for (; c + 7 < chunks; c += 8) {
-    f32x4 v[8];
+    T v[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = p4[(size_t)(c + k) * row];
+    for (int k = 0; k < 8; ++k) v[k] = p[(size_t)(c + k) * stride];
 #pragma unroll
     for (int k = 0; k < 8; k += 2) {
       a0 += v[k];
@@ -243,11 +254,15 @@ __device__ __forceinline__ f32x4 slab_reduce2_sum(const float* __restrict__ part
     }
   }
   for (; c + 1 < chunks; c += 2) {
-    a0 += p4[(size_t)c * row];
-    a1 += p4[(size_t)(c + 1) * row];
+    a0 += p[(size_t)c * stride];
+    a1 += p[(size_t)(c + 1) * stride];
   }
-  if (c < chunks) a0 += p4[(size_t)c * row];
+  if (c < chunks) a0 += p[(size_t)c * stride];
   return a0 + a1;
+}
+// the gradient of float4 column q from the partial rows in memory
+__device__ __forceinline__ f32x4 slab_reduce2_sum(const float* __restrict__ part, int Pst, int chunks, int q) {
+  return slab_part_sum(reinterpret_cast<const f32x4*>(part) + q, (size_t)(Pst >> 2), chunks);
 }
 
 // slabs [nwg][slab_stride(P)] at work, partials [chunks][slab_stride(P)] right after -> grad[P]

@@ -314,6 +314,23 @@ struct FzLossPtrs {
   const float* scal[8];
 };
 
+// The half of an Adam step's scalar bookkeeping that depends on nothing computed in the step: every
+// step counter += 1 and best_prev = the best loss so far.  One thread of the fused launch does it
+// ahead of the tile loop, so the one-launch step tail (jet_bf3.hip tail_one_kernel) finds both in
+// memory and none of its blocks waits for another.  The struct lives in device memory.
+#define FZ_MAX_COUNTERS 8
+struct FzPreBook {
+  double* c[FZ_MAX_COUNTERS];
+  int n, pad;
+  const float* best_loss;
+  float* best_prev;
+};
+__device__ __forceinline__ void step_prebook(const FzPreBook* __restrict__ pb) {
+  const int n = pb->n;
+  for (int i = 0; i < n && i < FZ_MAX_COUNTERS; ++i) *pb->c[i] += 1.0;
+  *pb->best_prev = *pb->best_loss;
+}
+
 struct FzParams {
   const float* X;
   const float* aux;
@@ -326,6 +343,7 @@ struct FzParams {
   const FzLossPtrs* lptrs;
   float* lpart;         // loss / scalar-gradient partials, row prow + blockIdx.x, nacc floats each
   int prow, nacc;
+  const FzPreBook* pre;  // the step's pre-bookkeeping (block 0, thread 0 of fz_body); nullptr: none
 };
 
 // J of stream s at tile point k from the NW waves' partial output dots jv[(w * S + s) * PT + k]
@@ -467,6 +485,9 @@ __device__ __forceinline__ void fz_body(const FzParams& P, char* lds_raw) {
     }
   };
   if (t0 < t1) fetch(t0);  // first, so its latency overlaps the set-up below
+  // the step's pre-bookkeeping: ordered against the previous and this step's tail by the kernel
+  // boundaries, read by nothing in this launch
+  if (P.pre != nullptr && gi == 0 && tid == 0) step_prebook(P.pre);
   fz_setup<WT, LM, F.xs>(P, aux, tid);
   f32x4 dk[LM][NR][NC];
   float lacc[LossF::NACC];  // this point-thread's loss / scalar-gradient sums (all tiles)

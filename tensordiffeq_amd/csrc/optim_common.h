@@ -74,12 +74,13 @@ static inline bool adam_args_fill(AdamArgs& args, const AdamGroup* src, int ngro
 
 // Per-step scalar bookkeeping (one thread): optional total = sum of the terms (fused loss, in
 // term order), history row [loss, terms...] at the device epoch, best loss / epoch and the
-// "improved" flag (NaN never improves), every Adam step counter += 1, epoch += 1.
+// "improved" flag (NaN never improves), every Adam step counter += 1, epoch += 1.  bump = false:
+// the counters were incremented ahead of the step (step_prebook, jet_fused.h).
 __device__ __forceinline__ void step_book_body(float* __restrict__ loss, const float* __restrict__ terms,
                                                int n_terms, int sum_terms, float* __restrict__ hist,
                                                int64_t hist_rows, int64_t* __restrict__ epoch,
                                                float* __restrict__ best_loss, int64_t* __restrict__ best_epoch,
-                                               int* __restrict__ improved, const Counters& cnt) {
+                                               int* __restrict__ improved, const Counters& cnt, bool bump = true) {
   float lv = *loss;
   if (sum_terms) {
     lv = 0.f;
@@ -98,6 +99,31 @@ __device__ __forceinline__ void step_book_body(float* __restrict__ loss, const f
     *best_epoch = ep;
   }
   *improved = imp;
-  for (int i = 0; i < cnt.n; ++i) *cnt.c[i] += 1.0;
+  if (bump)
+    for (int i = 0; i < cnt.n; ++i) *cnt.c[i] += 1.0;
   *epoch = ep + 1;
+}
+
+// Slot `slot` of the loss-kernel block partials lpart[n_rows][ns] summed over the rows, by one
+// wave (every lane calls it; lane 0 holds the sum).  The order is the one of a 256-thread
+// block reduction - leaf t = rows t, t + 256, ... added in turn, then the binary tree
+// t += t + 128, + 64, ..., + 1 - with lane l holding leaves l, l + 64, l + 128, l + 192 and the
+// last six levels across lanes, so it needs neither LDS nor a barrier and every wave of every
+// block that wants the sum gets the same bits.  It must stay the order of loss_reduce_kernel
+// (loss_fused.hip), which keeps the LDS form.  One wave reads 4 leaves where 256 threads read one
+// each: with more than 256 rows (mixed programs' side-chain rows, 500k-point steps) a lane adds
+// n_rows / 256 values per leaf in turn, as a thread of the LDS form did.
+__device__ __forceinline__ float loss_slot_sum(const float* __restrict__ lpart, int n_rows, int ns, int slot,
+                                               int lane) {
+  float leaf[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float s = 0.f;
+    for (int b = lane + 64 * k; b < n_rows; b += 256) s += lpart[(size_t)b * ns + slot];
+    leaf[k] = s;
+  }
+  float y = (leaf[0] + leaf[2]) + (leaf[1] + leaf[3]);
+#pragma unroll
+  for (int k = 32; k > 0; k >>= 1) y += __shfl_down(y, k, 64);
+  return y;
 }

@@ -98,6 +98,9 @@ class AdamEngine:
         # the optimizers' signature, the K-step graph, the captured step's forward scratch
         self._fsrc = self._grad = self._dp_buf = self._sig = self.graph_k = self._graph_saved = None
         self._sum_terms = False
+        # the one-launch tail's pre-bookkeeping (device FzPreBook) and the launches of the last tail
+        self._prebook_key = self._prebook_dev = self._best_prev = None
+        self.tail_launches = 0
         self._bind_opts()
         self._ensure_hist(n_steps_hint)
 
@@ -282,7 +285,8 @@ class AdamEngine:
                              f"{self.flat.numel()}")
         # persistent buffers: every captured step (the 1-step and the K-step graph) reads the weight
         # images the previous step's tail wrote into this one scratch
-        saved, work, pre, kw = self.points.run(pack=not in_graph)
+        one = self._tail_one()
+        saved, work, pre, kw = self.points.run(pack=not in_graph, prebook=self._prebook() if one else None)
         if self._grad is None:
             self._grad = torch.empty_like(self.flat)
         grad = self._grad
@@ -293,9 +297,34 @@ class AdamEngine:
                                "(set TDQ_FUSED_TAIL=0)")
         hi = prog.hi_op
         jet_hip.step_tail(saved, work, grad, fop, st, self.counters, packed[0], packed[1], st["best_flat"],
-                          write_images=in_graph, c_first=pre, gextra=hi.grad if hi is not None else None, **kw)
+                          write_images=in_graph, c_first=pre, gextra=hi.grad if hi is not None else None,
+                          best_prev=self._best_prev if one else None, **kw)
         self._tail_saved = saved
+        self.tail_launches = 1 if one else 2
         return fop.total
+
+    def _tail_one(self):
+        """The step ends in the ONE-launch tail (``tdq_step_tail1_bf3``; ``TDQ_TAIL_ONE=0``: never): a
+        single-process step on the one-launch fused step, whose launch carries the pre-bookkeeping -
+        its slab rows all reduce in the tail (first chunk 0, at most 8 chunks: one row per CU)."""
+        from .ops import jet_hip
+        fs = self.points.fused_step()
+        return (jet_hip.tail_one_enabled() and not self.dist.is_distributed and fs is not None and not fs.lo
+                and fs.layout in ("plain", "split") and fs.fop.n_terms + fs.fop.n_scal <= 64
+                and len(self.counters) <= 8)
+
+    def _prebook(self):
+        """The device ``FzPreBook`` of this engine's counters and best loss (rebuilt when a state
+        tensor was replaced; the first step of every capture is eager, so never inside one)."""
+        from .ops import jet_hip
+        st = self.state
+        key = tuple(c.data_ptr() for c in self.counters) + (st["best_loss"].data_ptr(),)
+        if self._prebook_key != key:
+            if self._best_prev is None:
+                self._best_prev = torch.zeros((), dtype=torch.float32, device=self.device)
+            self._prebook_dev = jet_hip.prebook_struct(self.counters, st["best_loss"], self._best_prev)
+            self._prebook_key = key
+        return self._prebook_dev
 
     def _dp_tail_phase_b(self, loss, grads, terms):
         """DP graph half after the all-reduce: bookkeeping, then Adam + snapshot + weight images."""
@@ -743,15 +772,18 @@ class PointPass:
             self._streams = [torch.cuda.Stream(device=self.flat.device) for _ in (self._ranges or ())]
         return self._ranges
 
-    def run(self, pack=True):
+    def run(self, pack=True, prebook=None):
         """Gradient slabs + loss partials of every point.  Returns ``(saved, work, first slab chunk
         of the tail, tail keyword arguments)`` - or ``None`` when not ``persistent`` and there is
-        neither a fused step nor a cut (the caller's single launches)."""
+        neither a fused step nor a cut (the caller's single launches).  ``prebook``: see
+        ``FusedStepOp.run`` (only a step on the fused launch may pass it)."""
         prog, fop = self.program, self.program.fused_op
         fs = self.fused_step()
+        if prebook is not None and fs is None:
+            raise RuntimeError("the pre-bookkeeping needs the one-launch fused step")
         if fs is not None:
             J, saved, work = self.buffers()
-            fs.run(saved, J, work, self.flat, pack=pack)
+            fs.run(saved, J, work, self.flat, pack=pack, prebook=prebook)
             return saved, work, 0, fs.tail_kw()
         rng = self.ranges()
         if not rng and not self.persistent:

@@ -19,7 +19,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TDQ_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "csrc", "libtdq_hip.so")
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _lock = threading.Lock()
 _lib = None
@@ -49,6 +49,10 @@ def _declare(lib):
         "tdq_jet_bf3_pack": (I, [P, P, I, I, P, I, I, I, P]),
         "tdq_step_tail_bf3": (I, [P, P, P, I, I, P, I, I, I, I, P, I, I, I, P, P, P] + [P, L, P, P, P, P]
                               + [P, I, P, I, P, I, P, I, P]),
+        "tdq_step_tail1_bf3": (I, [P, P, P, I, I, P, I, I, I, I, P, I, I, I, P, P, P] + [P, L, P, P, P, P]
+                               + [P, I, P, I, P, I, P, I, P, P]),
+        "tdq_step_prebook": (I, [P, P]),
+        "tdq_prebook_size": (I, []),
         "tdq_bf3_slab_geometry": (I, [I, I, P, I, I, I, I, P]),
         "tdq_slab_prereduce_bf3": (I, [P, I, I, P, I, I, I, I, I, I, P]),
         "tdq_dp_tail_a_bf3": (I, [P, P, I, I, P, I, I, I, I, P, I, I, I, P, P, P, I, P, I, I, P]),
@@ -56,7 +60,7 @@ def _declare(lib):
         "tdq_jet_bf3_scratch_floats": (L, [I, I, P, I, I, I]),
         "tdq_jet_bf3_slab_floats": (L, [I, I, P, I, I]),
         # persistent point-tile kernels (csrc/jet_fused.h) behind the split-bf16 entry points
-        "tdq_fused_step_launch": (I, [P, P, P, P, I, I, P, I, I, I, P, I, P, P, I, I, I, P]),
+        "tdq_fused_step_launch": (I, [P, P, P, P, I, I, P, I, I, I, P, I, P, P, I, I, I, P, P]),
         "tdq_fused_params_size": (I, []),
         "tdq_jet_fused_lds": (I, [I, P, I, I, I, I]),
         "tdq_device_cus": (I, []),

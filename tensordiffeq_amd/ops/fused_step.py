@@ -575,10 +575,13 @@ class FusedStepOp:
             self.fop2.partials = self.lpart[:self.prow * self.nacc]
             self._side = torch.cuda.Stream(device=dev)
 
-    def run(self, saved, J, work, flat, pack=True):
+    def run(self, saved, J, work, flat, pack=True, prebook=None):
         """The step's gradient slabs and loss partials (the fused launch; mixed programs: plus the
         high-order chain on a side stream, joined before return).  ``saved`` / ``J`` / ``work``: the
-        persistent step buffers of ``jet_hip.alloc_forward`` / ``alloc_backward``."""
+        persistent step buffers of ``jet_hip.alloc_forward`` / ``alloc_backward``.  ``prebook``
+        (``jet_hip.prebook_struct``; bf16 step only): the fused launch also does the pre-bookkeeping
+        of an Adam step that ends in the one-launch tail - never given under DP or for the bf16x3
+        objective."""
         lib = _lib.load()
         fop, cfg = self.fop, self.cfg
         if pack:
@@ -593,7 +596,8 @@ class FusedStepOp:
             rc = lib.tdq_fused_step_launch(self.func, _lib.ptr(self.X), _lib.ptr(scratch), _lib.ptr(work), self.N,
                                            cfg["d_in"], jet_hip._warg(cfg), cfg["d_out"], cfg["n_hidden"], S,
                                            spec_arr, self.G, _lib.ptr(fop.ptrs), _lib.ptr(self.lpart),
-                                           self.prow, self.nacc, int(self.lo), _lib.stream_ptr(flat.device))
+                                           self.prow, self.nacc, int(self.lo), _lib.ptr(prebook),
+                                           _lib.stream_ptr(flat.device))
             _lib.check(rc, "tdq_fused_step_launch")
 
         if side is None:

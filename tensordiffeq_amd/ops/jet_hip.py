@@ -8,6 +8,7 @@ allocator (and from the private pool while a HIP graph is being captured).
 from __future__ import annotations
 
 import ctypes
+import os
 
 import torch
 
@@ -231,9 +232,46 @@ def slab_prereduce(saved, work, c0, c1):
     _lib.check(rc, "tdq_slab_prereduce_bf3")
 
 
+class _PreBook(ctypes.Structure):
+    """csrc/jet_fused.h ``FzPreBook``."""
+    _fields_ = [("c", ctypes.c_void_p * 8), ("n", ctypes.c_int), ("pad", ctypes.c_int),
+                ("best_loss", ctypes.c_void_p), ("best_prev", ctypes.c_void_p)]
+
+
+def prebook_struct(counters, best_loss, best_prev):
+    """Device copy (a uint8 tensor) of the ``FzPreBook`` of a step's pre-bookkeeping: every step
+    counter += 1 and ``best_prev = best_loss``, done by the fused launch (``FusedStepOp.run(prebook=)``)
+    or :func:`step_prebook` ahead of the one-launch tail (:func:`step_tail` with ``best_prev``).
+    Not to be built inside a graph capture (a host-to-device copy)."""
+    lib = _lib.load()
+    if len(counters) > 8 or lib.tdq_prebook_size() != ctypes.sizeof(_PreBook):
+        raise ValueError("prebook_struct: more than 8 step counters / FzPreBook layout mismatch")
+    pb = _PreBook()
+    for i, c in enumerate(counters):
+        pb.c[i] = c.data_ptr()
+    pb.n = len(counters)
+    pb.best_loss, pb.best_prev = best_loss.data_ptr(), best_prev.data_ptr()
+    return torch.frombuffer(bytearray(bytes(pb)), dtype=torch.uint8).to(best_loss.device)
+
+
+def step_prebook(pre):
+    """The pre-bookkeeping of ``pre`` (:func:`prebook_struct`) as a launch of its own
+    (``tdq_step_prebook``) - for steps without a fused launch to carry it (tests)."""
+    _lib.check(_lib.load().tdq_step_prebook(_lib.ptr(pre), _lib.stream_ptr(pre.device)), "tdq_step_prebook")
+
+
+def tail_one_enabled():
+    """``TDQ_TAIL_ONE`` (on unless ``0``): the one-launch step tail; the native library reads the
+    same switch for the one-launch slab reduction of bf16 rows (``tdq_dp_tail_a_bf3``)."""
+    return os.environ.get("TDQ_TAIL_ONE", "1") != "0"
+
+
 def step_tail(saved, work, grad, fop, book, counters, group_array, n_groups, snapshot, write_images=True,
-              c_first=0, gextra=None, rows=0, lpart=None, n_lblocks=None):
-    """End of a single-process Adam step in two launches (csrc/jet_bf3.hip ``tdq_step_tail_bf3``):
+              c_first=0, gextra=None, rows=0, lpart=None, n_lblocks=None, best_prev=None):
+    """End of a single-process Adam step (csrc/jet_bf3.hip).  ``best_prev`` given: ONE launch
+    (``tdq_step_tail1_bf3``: a workgroup owns 256 theta columns from the slab rows to the updated
+    parameters) - the step's pre-bookkeeping (:func:`prebook_struct`) must have run since the
+    previous tail, ``c_first`` must be 0.  Else two launches (``tdq_step_tail_bf3``):
     slab reduction + loss reduction + bookkeeping, then the reduced gradient fused into Adam
     (theta, SA weights), the best-weights snapshot and - ``write_images`` - the next step's
     weight images.  ``book``: the engine's device state dict; ``group_array``: ctypes array of
@@ -246,7 +284,8 @@ def step_tail(saved, work, grad, fop, book, counters, group_array, n_groups, sna
     X, P, scratch, cfg, spec, S = saved
     hist = book["hist"]
     carr = (ctypes.c_void_p * max(1, len(counters)))(*[c.data_ptr() for c in counters])
-    rc = lib.tdq_step_tail_bf3(
+    one = best_prev is not None
+    rc = (lib.tdq_step_tail1_bf3 if one else lib.tdq_step_tail_bf3)(
         _lib.ptr(work), _lib.ptr(grad), _lib.ptr(scratch) if write_images else None,
         X.shape[0], cfg["d_in"], _warg(cfg), cfg["d_out"], cfg["n_hidden"], S, *_lo_args(cfg),
         _lib.ptr(fop.partials if lpart is None else lpart), fop.n_blocks if n_lblocks is None else int(n_lblocks),
@@ -256,8 +295,8 @@ def step_tail(saved, work, grad, fop, book, counters, group_array, n_groups, sna
         _lib.ptr(book["best_epoch"]), _lib.ptr(book["improved"]), ctypes.cast(carr, ctypes.c_void_p), len(counters),
         ctypes.cast(group_array, ctypes.c_void_p), n_groups,
         _lib.ptr(snapshot) if snapshot is not None else None, int(c_first), _lib.ptr(gextra), int(rows),
-        _lib.stream_ptr(X.device))
-    _lib.check(rc, "tdq_step_tail_bf3")
+        *([_lib.ptr(best_prev)] if one else []), _lib.stream_ptr(X.device))
+    _lib.check(rc, "tdq_step_tail1_bf3" if one else "tdq_step_tail_bf3")
 
 
 class JetMLPFunction(torch.autograd.Function):

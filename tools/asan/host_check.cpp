@@ -23,6 +23,8 @@ TDQ_STUB(bf3_fwd_w8)
 TDQ_STUB(bf3_bwd_w2)
 TDQ_STUB(bf3_bwd_w4)
 TDQ_STUB(bf3_bwd_w8)
+TDQ_STUB(bf3_fwd_w16)
+TDQ_STUB(bf3_bwd_w16)
 
 extern "C" {
 int64_t tdq_jet_bf3_scratch_floats(int N, int d_in, const int* widths, int n_hidden, int S, int lo);
