@@ -64,6 +64,14 @@ struct LFMeta {
   int n_groups, n_terms, n_scal, S, d_in, N, d_out;
 };
 
+// Seed mode (the Jacobian seeds of ONE loss output, tensordiffeq_amd/ops/ntk.py): group `group`,
+// instances [lo, lo + n) of it, one thread each from block 0 on; J / X / dJ hold `N` points (LFMeta.N) of
+// which slot k's instance i is point seg_off[k] + i (a re-laid point list: the offsets may be negative).
+// adj[f_out] = 1 replaces the loss seeds; no loss, no weight adjoint, no scalar-gradient reduction.
+struct LFSeed {
+  int group, out, lo, n, seg_off[LF_MAX_SLOTS];
+};
+
 __device__ __forceinline__ float block_sum(float v, float* red) {
   // 128 threads = 2 waves: DPP row sums, then 8 row partials through LDS
   v = row16_sum(v);
@@ -79,29 +87,35 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return s;  // valid in thread 0
 }
 
+template <bool SEED>
 __global__ void __launch_bounds__(LF_BLOCK) loss_fused_kernel(const int4* __restrict__ code,
                                                               const float* __restrict__ consts,
                                                               const LFOut* __restrict__ outs,
                                                               const LFGroup* __restrict__ groups, LFMeta meta,
                                                               const LFPtrs* __restrict__ ptrp, const float* __restrict__ J,
                                                               const float* __restrict__ X, float* __restrict__ dJ,
-                                                              float* __restrict__ partials, int blk0) {
+                                                              float* __restrict__ partials, int blk0,
+                                                              LFSeed seed) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ float red[LF_BLOCK / 16];
   __shared__ float acc[LF_MAX_TERMS + LF_MAX_SCAL];
   const int tid = threadIdx.x;
   const int blk = blk0 + (int)blockIdx.x;  // blk0: first block of a range launch
   int gi = 0;
-  for (int q = 1; q < meta.n_groups; ++q)
-    if (blk >= groups[q].block_off) gi = q;
+  if constexpr (SEED) {
+    gi = seed.group;
+  } else {
+    for (int q = 1; q < meta.n_groups; ++q)
+      if (blk >= groups[q].block_off) gi = q;
+  }
   const LFGroup G = groups[gi];
   const LFPtrs& ptr = *ptrp;
   // slot lookups by select (a runtime-indexed member array would be placed in scratch)
-  const int so0 = G.seg_off[0], so1 = G.seg_off[1];
+  const int so0 = SEED ? seed.seg_off[0] : G.seg_off[0], so1 = SEED ? seed.seg_off[1] : G.seg_off[1];
   auto seg_off = [&](int slot) { return slot == 0 ? so0 : so1; };
-  const int i = (blk - G.block_off) * LF_BLOCK + tid - G.phase;
-  const bool active = i >= 0 && i < G.n;
-  const int ii = active ? i : 0;
+  const int i = SEED ? seed.lo + blk * LF_BLOCK + tid : (blk - G.block_off) * LF_BLOCK + tid - G.phase;
+  const bool active = SEED ? (i < seed.lo + seed.n && i < G.n) : (i >= 0 && i < G.n);
+  const int ii = active ? i : (SEED ? seed.lo : 0);  // (an idle thread reads the range's first instance)
   float* V = lds;                               // [n_regs][LF_BLOCK]
   float* A = lds + G.n_regs * LF_BLOCK;         // [n_regs][LF_BLOCK]
   const int NP = meta.N;
@@ -150,7 +164,8 @@ __global__ void __launch_bounds__(LF_BLOCK) loss_fused_kernel(const int4* __rest
   }
 
   // ---- losses and seeds ----------------------------------------------------------------------
-  for (int o = 0; o < G.n_out; ++o) {
+  if (SEED && active) A[outs[G.out_off + seed.out].f * LF_BLOCK + tid] = 1.f;  // the one seed of seed mode
+  for (int o = 0; o < (SEED ? 0 : G.n_out); ++o) {
     const LFOut out = outs[G.out_off + o];
     const float f = V[out.f * LF_BLOCK + tid], w = V[out.w * LF_BLOCK + tid];
     const float contrib = active ? out.c * w * f * f : 0.f;
@@ -171,11 +186,13 @@ __global__ void __launch_bounds__(LF_BLOCK) loss_fused_kernel(const int4* __rest
         if (active) dJ[jidx(in.w, seg_off(in.z) + i)] = g;
         break;
       case OP_LAM:
-        if (active) ptr.dlam[in.z][i] = g;
+        if (!SEED && active) ptr.dlam[in.z][i] = g;
         break;
       case OP_SCAL: {
-        const float s = block_sum(active ? g : 0.f, red);
-        if (tid == 0) acc[meta.n_terms + in.z] += s;
+        if constexpr (!SEED) {
+          const float s = block_sum(active ? g : 0.f, red);
+          if (tid == 0) acc[meta.n_terms + in.z] += s;
+        }
         break;
       }
       case OP_ADD:
@@ -236,8 +253,10 @@ __global__ void __launch_bounds__(LF_BLOCK) loss_fused_kernel(const int4* __rest
     }
   }
 
-  __syncthreads();
-  if (tid < nslot_acc) partials[(size_t)blk * nslot_acc + tid] = acc[tid];
+  if constexpr (!SEED) {
+    __syncthreads();
+    if (tid < nslot_acc) partials[(size_t)blk * nslot_acc + tid] = acc[tid];
+  }
 }
 
 // losses[t] = sum_b partials[b][t] (fixed order); total = sum_t losses[t]; dscal[k] likewise
@@ -305,14 +324,48 @@ int tdq_loss_fused_range(const int* code, const float* consts, const void* outs,
   const size_t lds = (size_t)2 * max_regs * LF_BLOCK * sizeof(float);
   static bool attr = false;
   if (!attr) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel),
+    hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<false>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 120 * LF_BLOCK * (int)sizeof(float));
     attr = true;
   }
-  hipLaunchKernelGGL(loss_fused_kernel, dim3(nblk), dim3(LF_BLOCK), lds, st,
+  hipLaunchKernelGGL(loss_fused_kernel<false>, dim3(nblk), dim3(LF_BLOCK), lds, st,
                      reinterpret_cast<const int4*>(code), consts, reinterpret_cast<const LFOut*>(outs),
                      reinterpret_cast<const LFGroup*>(groups), meta, reinterpret_cast<const LFPtrs*>(ptrs), J, X,
-                     dJ, partials, blk0);
+                     dJ, partials, blk0, LFSeed{});
+  TDQ_CHECK_LAUNCH();
+  return 0;
+}
+
+// Seed mode: dJ = d f_out / d J for the instances [lo, lo + n) of group `group` (output `out` of that
+// group's program), J / X / dJ over N points with slot k's instance i at point seg_off[k] + i.  The
+// caller passes the group's own table entries (n_slots, n_regs, n_out, instance count) so that the range
+// and the offsets can be refused here: every point the launch touches must lie inside [0, N).
+int tdq_loss_seed(const int* code, const float* consts, const void* outs, const void* groups, const void* ptrs,
+                  int n_groups, int S, int d_in, int N, int d_out, const float* J, const float* X, float* dJ, int group,
+                  int out, int lo, int n, int seg_off0, int seg_off1, int g_n, int g_slots, int g_out, int g_regs,
+                  void* stream) {
+  if (n == 0) return 0;
+  if (d_out < 1 || d_out > LF_MAX_DOUT || S < 0 || S * d_out > 32 || n_groups < 1 || n_groups > LF_MAX_GROUPS ||
+      group < 0 || group >= n_groups || out < 0 || out >= g_out || g_regs < 1 || g_regs > 120 || g_slots < 1 ||
+      g_slots > LF_MAX_SLOTS || lo < 0 || n < 0 || (int64_t)lo + n > g_n || N < 1)
+    return (int)hipErrorInvalidValue;
+  const int so[LF_MAX_SLOTS] = {seg_off0, seg_off1};
+  for (int k = 0; k < g_slots; ++k)
+    if ((int64_t)so[k] + lo < 0 || (int64_t)so[k] + lo + n > N) return (int)hipErrorInvalidValue;
+  LFMeta meta{n_groups, 0, 0, S, d_in, N, d_out};
+  LFSeed seed{group, out, lo, n, {seg_off0, g_slots > 1 ? seg_off1 : seg_off0}};
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t lds = (size_t)2 * g_regs * LF_BLOCK * sizeof(float);
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(&loss_fused_kernel<true>),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 120 * LF_BLOCK * (int)sizeof(float));
+    attr = true;
+  }
+  hipLaunchKernelGGL(loss_fused_kernel<true>, dim3((n + LF_BLOCK - 1) / LF_BLOCK), dim3(LF_BLOCK), lds, st,
+                     reinterpret_cast<const int4*>(code), consts, reinterpret_cast<const LFOut*>(outs),
+                     reinterpret_cast<const LFGroup*>(groups), meta, reinterpret_cast<const LFPtrs*>(ptrs), J, X,
+                     dJ, static_cast<float*>(nullptr), 0, seed);
   TDQ_CHECK_LAUNCH();
   return 0;
 }

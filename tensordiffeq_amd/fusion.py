@@ -686,52 +686,67 @@ def _extra_syms(g, extra, scal_id, fl):
 # ------------------------------------------------------------------------------------------
 # reference executor (torch): the numerical definition of the fused kernel
 # ------------------------------------------------------------------------------------------
+def eval_group(P, n, stream, coord, val, lam, scal, device, dtype=None):
+    """Forward values of one group's program ``P`` over ``n`` instances with torch ops: the list of
+    register values.  The loads are callables: ``stream(slot, row, column)``, ``coord(slot, j)``,
+    ``val(k)``, ``lam(k)`` give ``(n,)`` tensors, ``scal(k)`` a 0-dim one."""
+    vals = []
+    for op, dst, a, b in P.code:
+        if op == OP["STREAM"]:
+            v = stream(a, b & ((1 << COL_SHIFT) - 1), b >> COL_SHIFT)
+        elif op == OP["COORD"]:
+            v = coord(a, b)
+        elif op == OP["VAL"]:
+            v = val(a)
+        elif op == OP["CONST"]:
+            v = torch.full((n,), P.consts[a], device=device, dtype=dtype)
+        elif op == OP["LAM"]:
+            v = lam(a)
+        elif op == OP["SCAL"]:
+            v = scal(a).reshape(()).expand(n)
+        else:
+            x = vals[a]
+            if op == OP["ADD"]:
+                v = x + vals[b]
+            elif op == OP["SUB"]:
+                v = x - vals[b]
+            elif op == OP["MUL"]:
+                v = x * vals[b]
+            elif op == OP["DIV"]:
+                v = x / vals[b]
+            elif op == OP["NEG"]:
+                v = -x
+            elif op == OP["POWI"]:
+                v = x ** b
+            elif op == OP["POWF"]:
+                v = x ** P.consts[b]
+            elif op == OP["SQUARE"]:
+                v = x * x
+            else:
+                v = {OP["SIN"]: torch.sin, OP["COS"]: torch.cos, OP["EXP"]: torch.exp,
+                     OP["TANH"]: torch.tanh, OP["LOG"]: torch.log, OP["SQRT"]: torch.sqrt}[op](x)
+        vals.append(v)
+    return vals
+
+
 def run_reference(fl, prog, J, lambdas, scalars):
     """Evaluate ``(loss_per_term, total)`` with torch autograd-able ops (same math as the kernel)."""
     losses = [None] * len(fl.term_names)
     for gr in fl.groups:
         P = gr.program
         n = gr.n
-        vals = []
-        for op, dst, a, b in P.code:
-            if op == OP["STREAM"]:
-                s = prog.segments[gr.segs[a]]
-                v = J[b & ((1 << COL_SHIFT) - 1), s.offset:s.offset + n, b >> COL_SHIFT]
-            elif op == OP["COORD"]:
-                s = prog.segments[gr.segs[a]]
-                v = prog.X_all[s.offset:s.offset + n, b]
-            elif op == OP["VAL"]:
-                v = fl.val_arrays[a].to(J.device)
-            elif op == OP["CONST"]:
-                v = torch.full((n,), P.consts[a], device=J.device)
-            elif op == OP["LAM"]:
-                k = fl.lam_slots[a]
-                lo, hi = fl.lam_offsets.get(k, (0, lambdas[k].shape[0]))
-                v = lambdas[k].reshape(-1)[lo:hi]
-            elif op == OP["SCAL"]:
-                v = scalars[a].reshape(()).expand(n)
-            else:
-                x = vals[a]
-                if op == OP["ADD"]:
-                    v = x + vals[b]
-                elif op == OP["SUB"]:
-                    v = x - vals[b]
-                elif op == OP["MUL"]:
-                    v = x * vals[b]
-                elif op == OP["DIV"]:
-                    v = x / vals[b]
-                elif op == OP["NEG"]:
-                    v = -x
-                elif op == OP["POWI"]:
-                    v = x ** b
-                elif op == OP["POWF"]:
-                    v = x ** P.consts[b]
-                elif op == OP["SQUARE"]:
-                    v = x * x
-                else:
-                    v = {OP["SIN"]: torch.sin, OP["COS"]: torch.cos, OP["EXP"]: torch.exp,
-                         OP["TANH"]: torch.tanh, OP["LOG"]: torch.log, OP["SQRT"]: torch.sqrt}[op](x)
-            vals.append(v)
+
+        def seg(slot):
+            return prog.segments[gr.segs[slot]]
+
+        def lam(a):
+            k = fl.lam_slots[a]
+            lo, hi = fl.lam_offsets.get(k, (0, lambdas[k].shape[0]))
+            return lambdas[k].reshape(-1)[lo:hi]
+
+        vals = eval_group(P, n, lambda a, row, col: J[row, seg(a).offset:seg(a).offset + n, col],
+                          lambda a, j: prog.X_all[seg(a).offset:seg(a).offset + n, j],
+                          lambda a: fl.val_arrays[a].to(J.device), lam, lambda a: scalars[a], J.device)
         for (fr, wr, t, c) in P.outputs:
             contrib = c * (vals[wr] * vals[fr] * vals[fr]).sum()
             losses[t] = contrib if losses[t] is None else losses[t] + contrib

@@ -8,7 +8,7 @@ newton_eager)``, ``get_loss_and_flat_grad``, ``predict(X_star, best_model=False)
 ``lambdas``, ``lambdas_map``, ``losses``, ``min_loss``, ``best_epoch``, ``best_model``.
 
 Implements the reference's *intent* where it is broken: ``Adaptive_type`` accepts
-ints and names (B14); SA works with minibatches and under DP (B5); DP shards points (B3) and
+ints and names, type 3 / ``"ntk"`` being the NTK weighting of ``ops/ntk.py`` (B14); SA works with minibatches and under DP (B5); DP shards points (B3) and
 reports the true global loss (B4); repeated ``fit`` calls resume (B6); L-BFGS runs under DP
 (B7); best weights are real snapshots (B8); the data-assimilation term is used (B17).
 """
@@ -36,12 +36,13 @@ _ADAPTIVE = {0: 0, "none": 0, "baseline": 0, "pinn": 0,
              3: 3, "ntk": 3}
 
 
-def parse_adaptive_type(a):
+def parse_adaptive_type(a, ntk=False):
+    """``ntk=True``: the caller implements NTK weighting (``CollocationSolverND.compile``)."""
     key = a.lower() if isinstance(a, str) else a
     if key not in _ADAPTIVE:
         raise Exception("Adaptive method invalid!")
     v = _ADAPTIVE[key]
-    if v == 3:
+    if v == 3 and not ntk:
         raise NotImplementedError("NTK adaptive weighting (Adaptive_type=3) is not implemented")
     return v
 
@@ -72,6 +73,9 @@ class CollocationSolverND:
         self.min_loss = {"adam": np.inf, "l-bfgs": np.inf, "overall": np.inf}
         self.best_model = {"adam": None, "l-bfgs": None, "overall": None}
         self.lambdas = self.dict_adaptive = self.lambdas_map = None
+        self.isNTK = False
+        self.ntk_every = 100
+        self.ntk_history = []   # (epoch, {term: T_k}, {term: lambda_k}) per NTK update
         self.data_x = self.data_t = self.data_s = None
         self._engine = None
         self._lbfgs_engine = None
@@ -86,7 +90,7 @@ class CollocationSolverND:
     def compile(self, layer_sizes, f_model, domain, bcs, Adaptive_type=0, dict_adaptive=None,
                 init_weights=None, g=None, dist=False, backend="auto", device=None,
                 periodic_legacy=False, seed=None, network=None, precision=None, metrics_path=None,
-                log_every=None, newton_precision=None, lbfgs_stop=None, newton_schedule=None):
+                log_every=None, newton_precision=None, lbfgs_stop=None, newton_schedule=None, ntk_every=100):
         from ..config import SolverConfig
         self.config = SolverConfig.from_env(backend=None if backend == "auto" else backend, precision=precision,
                                             seed=seed, metrics_path=metrics_path, log_every=log_every,
@@ -151,9 +155,27 @@ class CollocationSolverND:
         if ctx.is_distributed:
             ctx.broadcast_(self.u_model.flat.data)
 
-        self.Adaptive_type = parse_adaptive_type(Adaptive_type)
+        self.Adaptive_type = parse_adaptive_type(Adaptive_type, ntk=True)
         self.isAdaptive = self.Adaptive_type in (1, 2)
-        self.weight_outside_sum = self.Adaptive_type == 2
+        self.isNTK = self.Adaptive_type == 3
+        # NTK weights multiply the terms like type 2's: lambda_k * mean(f^2)
+        self.weight_outside_sum = self.Adaptive_type in (2, 3)
+        if self.isNTK:
+            if dict_adaptive is not None or init_weights is not None:
+                raise Exception("NTK weights are computed from the network, one per loss term, but weight vectors "
+                                "were provided. Set the weight vectors to \"none\" to continue")
+            if g is not None:
+                raise Exception("NTK weights multiply each loss term; a weight function g was provided. "
+                                "Set g to \"none\" to continue")
+            if backend == "autograd":
+                raise ValueError("NTK adaptive weighting needs the jet path (backend 'jet' or 'hip'), "
+                                 "backend 'autograd' was requested")
+            if int(ntk_every) < 1:
+                raise ValueError(f"ntk_every must be positive, got {ntk_every}")
+            self.ntk_every = int(ntk_every)
+            self.ntk_history = []
+            self._ntk = None
+            self._ntk_epoch = 0
         if not self.isAdaptive and dict_adaptive is not None and init_weights is not None:
             raise Exception("Adaptive weights are turned off but weight vectors were provided. "
                             "Set the weight vectors to \"none\" to continue")
@@ -171,6 +193,9 @@ class CollocationSolverND:
         self._engine = None
         self._lbfgs_engine = None
         self._state = None
+        if self.isNTK:
+            self._init_ntk_lambdas()
+            self._ntk_op()   # a loss the tracer cannot fuse is refused here
         for i, bc in enumerate(self.bcs):   # a target that does not fit the outputs is refused here
             if bc.isInit or bc.isDirichlect:
                 self._value_target(f"BC_{i} ({type(bc).__name__})", bc.val, getattr(bc, "outputs", None))
@@ -228,6 +253,67 @@ class CollocationSolverND:
             lmap[key.lower()] = idx
         self.lambdas, self.lambdas_map, self._lam_kind = lambdas, lmap, kinds
         self._lam_for = lam_for
+
+    def _init_ntk_lambdas(self):
+        """One scalar weight per loss term, 1.0: every residual output, then every BC, then the
+        assimilation term.  No optimizer owns them; :meth:`_ntk_update` overwrites them in place."""
+        self._n_res = self._residual_count()
+        keys = [("residual", k) for k in range(self._n_res)] + [("bc", i) for i in range(len(self.bcs))]
+        if self.assimilate:
+            keys.append(("data", 0))
+        self.lambdas = [torch.ones((), dtype=torch.float32, device=self.device) for _ in keys]
+        self._lam_for = {k: i for i, k in enumerate(keys)}
+        self._lam_kind = ["residual" if k[0] == "residual" else "bc" for k in keys]
+        self.lambdas_map = {"residual": [i for i, k in enumerate(keys) if k[0] == "residual"],
+                            "bcs": [i for i, k in enumerate(keys) if k[0] == "bc"]}
+        if self.assimilate:
+            self.lambdas_map["data"] = [len(keys) - 1]
+
+    def _ntk_op(self):
+        """The trace evaluator of the full-batch program (``ops/ntk.py``), rebuilt with the program."""
+        from ..ops import ntk
+        prog = self.program()
+        if self._ntk is None or self._ntk.prog is not prog:
+            self._ntk = ntk.build(prog, self.lambdas)
+        return self._ntk
+
+    def _ntk_traces(self):
+        """``(terms, T)``: the weighted terms of the full-batch program and their global traces (a
+        float64 CPU vector; under DP the all-reduced sum of the ranks' traces - the program's
+        coefficients already carry the global means and the 1/world of replicated terms)."""
+        op = self._ntk_op()
+        prog = op.prog
+        T = op.traces().detach().to(torch.float32)
+        ctx = self.dist_ctx
+        if ctx.is_distributed:
+            T = T.clone()
+            ctx.all_reduce_(T)
+        return [t for t in prog.terms if t.lam is not None], T.double().cpu()
+
+    def ntk_traces(self):
+        """``{term name: T_k}``: the NTK trace of every loss term at the current parameters."""
+        terms, T = self._ntk_traces()
+        names = [t.name for t in self._ntk_op().prog.terms]
+        return {t.name: float(T[names.index(t.name)]) for t in terms}
+
+    def _ntk_update(self, epoch):
+        """``lambda_k = sum_j T_j / T_k``, written in place: captured step graphs, the one-launch fused
+        step and the L-BFGS objective read the weights through their scalar pointers."""
+        from ..ops import ntk
+        from .loss import _warn_once
+        terms, T = self._ntk_traces()
+        names = [t.name for t in self._ntk_op().prog.terms]
+        Tk = torch.stack([T[names.index(t.name)] for t in terms])
+        prev = torch.stack([self.lambdas[t.lam].detach().double().cpu() for t in terms])
+        lam, ok = ntk.weights(Tk, prev)
+        if not bool(ok.all()):
+            bad = [t.name for t, o in zip(terms, ok.tolist()) if not o]
+            _warn_once(f"NTK weighting: the trace of {bad} is not positive and finite; the term keeps its weight")
+        with torch.no_grad():
+            for t, v in zip(terms, lam.tolist()):
+                self.lambdas[t.lam].copy_(torch.tensor(v, dtype=torch.float32))
+        self.ntk_history.append((int(epoch), {t.name: float(v) for t, v in zip(terms, Tk)},
+                                 {t.name: float(self.lambdas[t.lam]) for t in terms}))
 
     def compile_data(self, x, t, y):
         if not self.assimilate:
@@ -309,7 +395,7 @@ class CollocationSolverND:
                             np.reshape(np.asarray(self.data_t), (-1, 1))])
             s = prog.add_segment("data", Xd)
             val = self._data_target()
-            prog.add_term(Term("Data", "data", seg=s, val=val, scale=rep_scale))
+            prog.add_term(Term("Data", "data", seg=s, val=val, scale=rep_scale, lam=self._lam_for.get(("data", 0))))
         Xr = self.X_f_local
         n_glob = self.N_f
         if batch is not None:
@@ -384,7 +470,8 @@ class CollocationSolverND:
 
     @property
     def variables(self):
-        return [self._flat()] + list(self.lambdas or [])
+        # (NTK weights are not trained: no gradient is taken with respect to them)
+        return [self._flat()] + ([] if self.isNTK else list(self.lambdas or []))
 
     def _outside_sum_weights(self):
         """Per-point residual weights enter through MSE's outside sum (Adaptive_type 2 without
@@ -433,10 +520,14 @@ class CollocationSolverND:
         eng = self._programs.get(key)
         prog = self.program(batch)
         if eng is None:
-            groups = [ParamGroup([self._flat()], lambda: self.tf_optimizer, 1.0),
-                      ParamGroup(self.lambdas, lambda: self.tf_optimizer_weights, -1.0,
-                                 self._lam_replicated())]
-            eng = AdamEngine(self, prog, groups, n_steps_hint=n_hint, lambdas=self.lambdas)
+            groups = [ParamGroup([self._flat()], lambda: self.tf_optimizer, 1.0)]
+            bind = None
+            if self.isNTK:   # the weights enter the loss but no optimizer owns them
+                bind = lambda alias: {"params": alias[0], "lambdas": self.lambdas}  # noqa: E731
+            else:
+                groups.append(ParamGroup(self.lambdas, lambda: self.tf_optimizer_weights, -1.0,
+                                         self._lam_replicated()))
+            eng = AdamEngine(self, prog, groups, n_steps_hint=n_hint, lambdas=self.lambdas, bind=bind)
             self._programs[key] = eng
         return eng
 
@@ -493,12 +584,27 @@ class CollocationSolverND:
 
             t_adam = time.perf_counter()
             self._prebuild_lbfgs_objective()
-            if batches == [None]:
+            if batches == [None] and self.isNTK:
+                # segments between NTK updates: the weights change in place, the captured step stays
+                eng = self._get_engine(None, tf_iter)
+                done = 0
+                while done < tf_iter:
+                    if self._ntk_epoch % self.ntk_every == 0:
+                        self._ntk_update(self._ntk_epoch)
+                    n = min(tf_iter - done, self.ntk_every - self._ntk_epoch % self.ntk_every)
+                    eng.run(n, progress=lambda k, loss, base=done: progress(base + k, loss), log_every=self.log_every)
+                    done += n
+                    self._ntk_epoch += n
+            elif batches == [None]:
                 eng = self._get_engine(None, tf_iter)
                 eng.run(tf_iter, progress=progress, log_every=self.log_every)
             else:
                 engines = [self._get_engine(b, tf_iter * len(batches)) for b in batches]
                 for ep in range(tf_iter):
+                    if self.isNTK:   # the traces always come from the full-batch program
+                        if self._ntk_epoch % self.ntk_every == 0:
+                            self._ntk_update(self._ntk_epoch)
+                        self._ntk_epoch += 1
                     for eng in engines:
                         loss = eng.run(1, use_graph=False)
                     if (ep + 1) % self.log_every == 0 or ep + 1 == tf_iter:

@@ -19,7 +19,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TDQ_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "csrc", "libtdq_hip.so")
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _lock = threading.Lock()
 _lib = None
@@ -84,6 +84,11 @@ def _declare(lib):
         "tdq_loss_fused_range": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, I, I, I, I, P]),
         "tdq_loss_meta_sizes": (I, [P]),
         "tdq_loss_reduce_partials": (I, [P, I, I, I, P, P, P, I, P]),
+        # NTK traces (csrc/ntk_trace.hip, the loss interpreter's seed mode; ops/ntk.py)
+        "tdq_jet_pad_kp": (I, [P, P, I, I, I, I, P]),
+        "tdq_ntk_norm": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P, P]),
+        "tdq_ntk_sum": (I, [P, I, P, P]),
+        "tdq_loss_seed": (I, [P, P, P, P, P, I, I, I, I, I, P, P, P] + [I] * 10 + [P]),
         "tdq_lbfgs_nst": (I, []),
         "tdq_lbfgs_ticket_ints": (I, []),
         "tdq_lbfgs_update": (I, [P] * 14 + [I] * 6 + [D] * 4 + [I, P]),

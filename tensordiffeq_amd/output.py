@@ -31,3 +31,5 @@ def print_screen(model, discovery_model=False):
         pass
     if prog is not None:
         print(f"\nbackend: {prog.backend}" + (f"  streams: {prog.plan.streams}" if prog.plan else ""))
+    if getattr(model, "isNTK", False):
+        print(f"adaptive weights: NTK (one weight per loss term, recomputed every {model.ntk_every} Adam steps)")

@@ -1,0 +1,146 @@
+"""Cost of the NTK weight update at the AC-SA shape ([2, 128 x 4, 1], 50k collocation points + the
+initial and periodic boundary points, ``Adaptive_type="ntk"``, bf16 training precision):
+
+    python tools/ntk_timing.py [--n-f 50000] [--reps 9] [--out profiles/NAME.json]
+
+* one full ``NTKTraceOp.traces()`` call (every forward, seed, norm and sum launch of every loss output);
+* the norm kernel of the residual output (``tdq_ntk_norm``; with and without the weight-image launch)
+  against the existing exact-fp32 backward (``tdq_jet_bwd``: weight images, backward kernel, slab
+  reduction) over the same points, seeds and saved streams - the norm kernel runs the backward's adjoint
+  chain without the dK GEMMs;
+* the Adam step, for the overhead per step at ``ntk_every=100``.
+
+Every time is a host clock around launches that end in a device synchronise, after warm-up calls; the
+two kernels alternate inside each repetition; medians and ranges over the repetitions.  Needs a GPU."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def build(n_f, device):
+    import math
+    import numpy as np
+    import torch
+    import tensordiffeq_amd as tdq
+    from tensordiffeq_amd.boundaries import IC, DomainND, periodicBC
+    tdq.set_seed(0)
+    D = DomainND(["x", "t"], time_var="t")
+    D.add("x", [-1.0, 1.0], 512)
+    D.add("t", [0.0, 1.0], 201)
+    D.generate_collocation_points(n_f)
+
+    def deriv_model(u_model, x, t):
+        u = u_model(torch.cat([x, t], 1))
+        return u, tdq.grad(u, x)
+
+    def f_model(u_model, x, t):
+        u = u_model(torch.cat([x, t], 1))
+        return tdq.grad(u, t) - 0.0001 * tdq.grad(tdq.grad(u, x), x) + 5.0 * u ** 3 - 5.0 * u
+
+    bcs = [IC(D, [lambda x: x ** 2 * np.cos(math.pi * x)], var=[["x"]]), periodicBC(D, ["x"], [deriv_model])]
+    m = tdq.CollocationSolverND(verbose=False)
+    m.compile([2, 128, 128, 128, 128, 1], f_model, D, bcs, Adaptive_type="ntk", ntk_every=100, backend="hip",
+              device=device, precision="bf16", newton_precision="bf16x3")
+    return m
+
+
+def _stat(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v), "runs": v}
+
+
+def main(argv=None):
+    import torch
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--n-f", type=int, default=50000)
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--inner", type=int, default=5, help="launches per timed window")
+    ap.add_argument("--steps", type=int, default=300, help="Adam steps per timed block")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        sys.exit("tools/ntk_timing.py measures on the GPU; none found")
+    from tensordiffeq_amd.ops import jet_hip, ntk
+    m = build(a.n_f, "cuda")
+    op = m._ntk_op()
+    assert op.kind == "hip", m.program().reasons
+    prog, fop = op.prog, op.fop
+    sync = torch.cuda.synchronize
+
+    def timed(fn, n=1):
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        sync()
+        return 1e3 * (time.perf_counter() - t0) / n
+
+    for _ in range(3):
+        op.traces()
+    traces = [timed(op.traces) for _ in range(a.reps)]
+
+    # the residual output: its group, one forward over its points, its seeds
+    gi = [i for i, gr in enumerate(fop.fl.groups) if gr.n == a.n_f][0]
+    gr = fop.fl.groups[gi]
+    off = prog.segments[gr.segs[0]].offset
+    X = prog.X_all[off:off + gr.n]
+    P = prog.net.flat.detach()
+    J, saved = jet_hip.forward_raw(X, P, prog.net, prog.plan, precision="fp32")
+    dJ = ntk.seeds(fop, gi, 0, J, X, torch.zeros_like(J), 0, gr.n, [0])
+    Kp = ntk.pad_kp(P, op.cfg)
+    n2 = torch.zeros(gr.n, device="cuda")
+    grad = torch.empty_like(P)
+    runs = {"norm": lambda: ntk.instance_norms(saved, dJ, Kp, gr.n, out=n2),
+            "pad_norm": lambda: (ntk.pad_kp(P, op.cfg, Kp), ntk.instance_norms(saved, dJ, Kp, gr.n, out=n2)),
+            "jet_bwd": lambda: jet_hip.backward_raw(saved, dJ, grad=grad),
+            "jet_fwd": lambda: jet_hip.forward_raw(X, P, prog.net, prog.plan, precision="fp32")}
+    for fn in runs.values():
+        timed(fn, 3)
+    ms = {k: [] for k in runs}
+    for _ in range(a.reps):
+        for k, fn in runs.items():      # alternating inside every repetition
+            ms[k].append(timed(fn, a.inner))
+
+    m.fit(tf_iter=64)
+    sync()
+    step = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        m.fit(tf_iter=a.steps)    # a multiple of ntk_every: includes steps / 100 weight updates
+        sync()
+        step.append(1e3 * (time.perf_counter() - t0) / a.steps)
+    m2 = build(a.n_f, "cuda")
+    m2.ntk_every = 10 ** 9        # the same program and weights, never updated after epoch 0
+    m2.fit(tf_iter=64)
+    sync()
+    plain = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        m2.fit(tf_iter=a.steps)
+        sync()
+        plain.append(1e3 * (time.perf_counter() - t0) / a.steps)
+
+    out = {"n_f": a.n_f, "points": int(prog.X_all.shape[0]), "layers": list(prog.net.layer_sizes), "S": op.S,
+           "outputs": len(op.outputs), "forwards_per_traces_call": len(op.launches),
+           "traces_ms": _stat(traces), "kernels_ms": {k: _stat(v) for k, v in ms.items()},
+           "adam_ms_per_step_ntk_every_100": _stat(step), "adam_ms_per_step_no_update": _stat(plain)}
+    nm, bw = out["kernels_ms"]["pad_norm"], out["kernels_ms"]["jet_bwd"]
+    out["pad_norm_over_jet_bwd"] = nm["median"] / bw["median"]
+    # "no slower" unless the medians differ by more than three times the backward's own range
+    out["norm_slower_than_bwd"] = bool(nm["median"] - bw["median"] > 3 * (bw["max"] - bw["min"]))
+    out["traces_ms_per_step_at_ntk_every_100"] = out["traces_ms"]["median"] / 100
+    out["overhead_per_step_fraction"] = out["traces_ms_per_step_at_ntk_every_100"] / statistics.median(plain)
+    print(json.dumps(out, indent=1))
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(out, fh, indent=1)
+    return out
+
+
+if __name__ == "__main__":
+    main()
