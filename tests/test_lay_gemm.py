@@ -7,7 +7,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1000, 300, 256), (130, 512, 512), (777, 1, 200), (64, 129, 33), (4096, 256, 160)]
+# (63, 36, 5), (1, 20, 6): the HB = dJ Ko^T GEMMs of the 5 <= d_out <= 64 branch (K = d_out below one k-step,
+# M below one tile)
+SHAPES = [(1000, 300, 256), (130, 512, 512), (777, 1, 200), (64, 129, 33), (4096, 256, 160), (63, 36, 5), (1, 20, 6)]
 TOL = {"fp32": 2e-6, "bf16x3": 2e-5, "bf16": 1.5e-2}
 
 
@@ -31,7 +33,8 @@ def test_nn_matches_fp64(M, N, K, prec):
 
 
 @pytest.mark.parametrize("prec", ["fp32", "bf16x3", "bf16"])
-@pytest.mark.parametrize("L,Ma,Nb", [(20000, 256, 256), (3001, 129, 512), (100, 64, 1), (65536, 512, 33)])
+@pytest.mark.parametrize("L,Ma,Nb", [(20000, 256, 256), (3001, 129, 512), (100, 64, 1), (65536, 512, 33),
+                                     (7, 36, 6)])   # L below one 32-row chunk
 def test_tn_matches_fp64(L, Ma, Nb, prec):
     from tensordiffeq_amd.ops import jet_layered
     torch.manual_seed(1)
