@@ -60,7 +60,8 @@ def main(argv=None):
     ap = parser(__doc__.splitlines()[0], iters=10000, newton=0, n_f=10000)
     ap.add_argument("--ntk-every", type=int, default=100, help="Adam steps between NTK weight updates")
     ap.add_argument("--width", type=int, default=64,
-                    help="hidden width, three hidden layers (5 streams: the NTK trace kernels take widths <= 64)")
+                    help="hidden width, three hidden layers (5 streams: the norm kernel takes widths <= 64, the "
+                         "layer-wise trace path widths <= 128)")
     args = ap.parse_args(argv)
     res = {}
     for tag, adaptive in (("ntk", True), ("baseline", False)):

@@ -19,7 +19,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TDQ_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "csrc", "libtdq_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _lock = threading.Lock()
 _lib = None
@@ -88,6 +88,8 @@ def _declare(lib):
         "tdq_jet_pad_kp": (I, [P, P, I, I, I, I, P]),
         "tdq_ntk_norm": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P, P]),
         "tdq_ntk_sum": (I, [P, I, P, P]),
+        # one layer's Gram share of the norms from fp32 planes (csrc/ntk_gram.hip, the layer-wise NTK path)
+        "tdq_ntk_gram": (I, [P, L, I, P, L, I, I, I, I, I, I, I, P, P]),
         "tdq_loss_seed": (I, [P, P, P, P, P, I, I, I, I, I, P, P, P] + [I] * 10 + [P]),
         "tdq_lbfgs_nst": (I, []),
         "tdq_lbfgs_ticket_ints": (I, []),

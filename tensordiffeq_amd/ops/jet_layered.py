@@ -529,3 +529,61 @@ def backward_raw(saved, dJ, grad=None):
             dK0[spec[3 * s + 1]] += ZB0[s].sum(dim=0)
     torch.sum(ZB0[0], dim=0, out=gb0)
     return grad
+
+
+def input_jet_plane(X, spec, S):
+    """The input jets as a plane ``[S*N, d_in]``: ``x`` on the value stream, ``e_a`` on a first-order
+    stream in variable ``a``, 0 on second-order streams (layer 0's ``H`` of :func:`adjoint_planes`)."""
+    N, d_in = X.shape
+    H = torch.zeros((S, N, d_in), dtype=X.dtype, device=X.device)
+    H[0] = X
+    for s in range(1, S):
+        if spec[3 * s] == 1:
+            H[s, :, spec[3 * s + 1]] = 1.0
+    return H.view(S * N, d_in)
+
+
+@torch.no_grad()
+def adjoint_planes(saved, dJ):
+    """The adjoint chain of :func:`backward_raw` without the weight-gradient GEMMs, the bias column
+    sums and the layer-0 gradient partials: yields, from the output layer down to layer 0, each dense
+    layer's ``(H_{l-1}, Z_l)`` - its input rows ``[S*N, in]`` and the adjoints of its pre-activations
+    ``[S*N, out]``, fp32 row-major planes (row ``s N + n`` = stream ``s`` of point ``n``).  The output
+    layer's ``Z`` is ``dJ`` itself, layer 0's ``H`` the input jets (:func:`input_jet_plane`).  Serves
+    every branch of an fp32 :func:`forward_raw`; a ``Z`` plane may be dropped once the next pair has
+    been drawn."""
+    _, X, P, net, spec, Hs, Ho, prec, fused = saved
+    if prec != "fp32":
+        raise ValueError("adjoint_planes reads the fp32 planes of an fp32 forward_raw")
+    ws = net.weights(P)
+    S, N, d_out = dJ.shape
+    dJ = dJ.contiguous()
+    Ko, _ = ws[-1]
+    last = len(ws) - 2
+
+    def plane(H):
+        return H.view(S * N, H.shape[-1])
+
+    yield plane(Hs[last]), dJ.view(S * N, d_out)
+    W = Ko.shape[0]
+    if fused and d_out <= 4:   # the last hidden layer's adjoint with HB = dJ Ko^T formed in the kernel
+        ZB = torch.empty((S * N, W), dtype=torch.float32, device=X.device)
+        lib = _lib.load(required=True)
+        _lib.check(lib.tdq_lay_out_bwd(1, EPI_BWD, S, _spec_c(spec), _lib.ptr(dJ), d_out, _lib.ptr(Ko.contiguous()),
+                                       _lib.ptr(Hs[last]), None, N, W, _lib.ptr(ZB), None, None, None, 0,
+                                       _lib.stream_ptr(X.device)), "tdq_lay_out_bwd")
+    else:
+        if d_out == 1:
+            HB = (dJ.view(S * N, 1) * Ko.view(1, -1)).view(S, N, W)
+        else:
+            HB = _mm_bt(_Op(dJ.view(S * N, d_out), prec), Ko, prec).view(S, N, W)
+        ZB = plane(_epi(False, HB, Hs[last].view(S, N, W), None, spec, prec)[0])
+    for i in range(last, 0, -1):
+        yield plane(Hs[i - 1]), ZB
+        K, _ = ws[i]
+        if fused:   # HB_{i-1} = ZB_i K_i^T with layer i-1's adjoint jet in the GEMM epilogue, down to layer 0
+            ZB = _nnj(EPI_BWD, prec, spec, S, N, _Op(ZB, prec), K, H=Hs[i - 1])[0]
+        else:
+            HB = _mm_bt(_Op(ZB, prec), K, prec).view(S, N, K.shape[0])
+            ZB = plane(_epi(False, HB, Hs[i - 1].view(S, N, K.shape[0]), None, spec, prec)[0])
+    yield input_jet_plane(X, spec, S), ZB

@@ -17,6 +17,9 @@ is ``sum_r H[r] Z[r]^T``, so
 * :class:`NTKTraceOp` - the HIP path: per group chunk one exact-fp32 forward (``tdq_jet_fwd``), per
   output the seed launch (``tdq_loss_seed``: ``d f_o / d J`` from the loss interpreter) and the norm
   launch (``tdq_ntk_norm``, csrc/ntk_trace.hip), then a fixed-order sum.
+* :class:`LayeredNTKOp` - the HIP path beyond that kernel's register envelope (5-8 streams at width 128,
+  unequal widths): the layer-wise engine's fp32 forward and adjoints-only pass, then per dense layer one
+  Gram-product launch (``tdq_ntk_gram``, csrc/ntk_gram.hip) on the ``(H_{l-1}, Z_l)`` planes.
 * :class:`TorchNTK` - the same formula on the torch jet (CPU, ``backend="jet"``, and any plan or
   network outside the HIP envelope): the adjoints ``Z`` of all instances come from ONE reverse pass per
   output, because an instance's ``f`` only reads its own rows.
@@ -330,10 +333,201 @@ class NTKTraceOp:
         return self.norms[(gi, oi)]
 
 
+# ------------------------------------------------------------------------------------------
+# layer-wise HIP path
+# ------------------------------------------------------------------------------------------
+def _gram_check(H, Z, S, N, n_inst, offA, offB, n2):
+    for name, t in (("H", H), ("Z", Z)):
+        if t.dim() != 2 or t.shape[0] != S * N or t.dtype != H.dtype or not t.is_floating_point() \
+                or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            raise ValueError(f"tdq_ntk_gram: {name} must be a floating ({S * N}, W) row-major plane, got "
+                             f"{tuple(t.shape)} strides {tuple(t.stride())}")
+    if not 1 <= S <= 8 or n_inst < 0 or offA < 0 or offA + n_inst > N or (offB is not None and (
+            offB < 0 or offB + n_inst > N)):
+        raise ValueError(f"tdq_ntk_gram: S {S}, instances [{offA}, {offA + n_inst}) / pair offset {offB} outside "
+                         f"1..8 streams of {N} points")
+    if n2.dtype != H.dtype or not n2.is_contiguous() or n2.numel() != n_inst:
+        raise ValueError(f"tdq_ntk_gram: n2 must be a contiguous ({n_inst},) tensor of the planes' dtype")
+
+
+def gram_norms(H, Z, S, N, n_inst, offA=0, offB=None, out=None, accumulate=False):
+    """One dense layer's share of the per-instance norms (``tdq_ntk_gram``, csrc/ntk_gram.hip):
+    ``out[i] (+)= sum_{r,r'} (Z[r].Z[r']) (H[r].H[r']) + ||sum_{value rows} Z[r]||^2`` over the rows of
+    instance ``i`` - the ``S`` streams of point ``offA + i``, and of ``offB + i`` in pair mode.  ``H`` / ``Z``:
+    float32 ``(S*N, W)`` planes (row ``s N + n``), each with its own row stride."""
+    from . import _lib
+    if out is None:
+        out = torch.zeros(max(0, n_inst), device=H.device)
+    # the kernel trusts the planes' extent and n2's length; it refuses bad geometry itself
+    for name, t in (("H", H), ("Z", Z)):
+        if t.dim() != 2 or t.shape[0] != S * N or t.dtype != torch.float32 or t.stride(1) != 1 or not t.is_cuda:
+            raise ValueError(f"tdq_ntk_gram: {name} must be a float32 ({S * N}, W) row-major device plane, got "
+                             f"{tuple(t.shape)} strides {tuple(t.stride())}")
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != max(0, n_inst) or not out.is_cuda:
+        raise ValueError(f"tdq_ntk_gram: n2 must be a contiguous float32 ({n_inst},) device tensor")
+    rc = _lib.load(required=True).tdq_ntk_gram(
+        _lib.ptr(H), H.stride(0), H.shape[1], _lib.ptr(Z), Z.stride(0), Z.shape[1], int(S), int(N), int(offA),
+        -1 if offB is None else int(offB), int(n_inst), int(bool(accumulate)), _lib.ptr(out),
+        _lib.stream_ptr(H.device))
+    _lib.check(rc, "tdq_ntk_gram")
+    return out
+
+
+def gram_norms_torch(H, Z, S, N, n_inst, offA=0, offB=None, out=None, accumulate=False):
+    """The torch mirror of :func:`gram_norms` (same contract, the planes' own dtype): the CPU path of
+    :class:`LayeredNTKOp` and the formula of the tests."""
+    _gram_check(H, Z, S, N, n_inst, offA, offB, out if out is not None else H.new_empty(max(0, n_inst)))
+    offs = [offA] if offB is None else [offA, offB]
+
+    def rows(V):  # (n_inst, R, W)
+        V = V.view(S, N, V.shape[1]) if V.is_contiguous() else V.reshape(S, N, V.shape[1])
+        return torch.cat([V[:, o:o + n_inst] for o in offs], dim=0).transpose(0, 1)
+
+    Zr, Hr = rows(Z), rows(H)
+    term = ((Zr @ Zr.transpose(1, 2)) * (Hr @ Hr.transpose(1, 2))).sum((1, 2))
+    term = term + Zr[:, ::S].sum(1).square().sum(1)
+    if out is None:
+        return term
+    if accumulate:
+        out += term
+    else:
+        out.copy_(term)
+    return out
+
+
+def layered_enabled():
+    """``TDQ_NTK_LAYERED=0`` keeps the programs of :class:`LayeredNTKOp` on the torch path (the A/B switch of
+    tools/ntk_timing.py); on by default."""
+    import os
+    return os.environ.get("TDQ_NTK_LAYERED", "1") != "0"
+
+
+def layered_reason(prog):
+    """None when :class:`LayeredNTKOp` serves the program on the GPU, else why not: the HIP backend, a
+    fused, unmixed program of order <= 2 with S <= 8, hidden widths <= 128 (equal or not), <= 16 hidden
+    layers, d_in <= 8, d_out <= 4."""
+    if prog.device.type != "cuda" or prog.backend != "hip":
+        return "the program does not run on the HIP backend"
+    if prog.fused_op is None:
+        return "the loss program is not fused"
+    if prog.mixed:
+        return f"derivative order {prog.plan_hi.order} > 2"
+    sizes = list(prog.net.layer_sizes)
+    if prog.plan.order > 2 or prog.plan.S > 8:
+        return f"order {prog.plan.order}, {prog.plan.S} streams"
+    # (the kernels take any width; 128 keeps the networks wider than that on the path their tests pin)
+    if max(sizes[1:-1]) > 128 or len(sizes) - 2 > 16 or sizes[0] > 8 or sizes[-1] > 4:
+        return f"layers {sizes} outside widths <= 128, <= 16 hidden layers, d_in <= 8, d_out <= 4"
+    return None
+
+
+class LayeredNTKOp:
+    """Traces on the layer-wise engine, for programs beyond :class:`NTKTraceOp`'s register envelope
+    (5-8 streams at width 128, unequal widths).  Per launch group one exact-fp32 layered forward
+    (:func:`.jet_layered.forward_raw`), per output the seed launch (``tdq_loss_seed``), the adjoints-only
+    pass (:func:`.jet_layered.adjoint_planes`) and one ``tdq_ntk_gram`` per dense layer, then the
+    fixed-order ``tdq_ntk_sum``.  Same interface, buffers, chunking and bitwise repeatability as
+    :class:`NTKTraceOp`.  Without a GPU (``fop=None``) the seeds come from autograd through the torch
+    interpreter and the Gram step from :func:`gram_norms_torch`."""
+
+    kind = "hip-layered"
+
+    def __init__(self, prog, fl, lambdas, fop=None, chunk=CHUNK):
+        self.prog, self.fl, self.lambdas, self.fop = prog, fl, lambdas, fop
+        self.S = prog.plan.S
+        self.d_out = prog.net.layer_sizes[-1]
+        dev = prog.device
+        self.hip = fop is not None and dev.type == "cuda"
+        self.outputs = outputs(fl)
+        self.launches = []   # (group, lo, m, slots) per forward
+        for gi, gr in enumerate(fl.groups):
+            step = max(1, int(chunk) // len(gr.segs))
+            self.launches += [(gi, lo, min(gr.n, lo + step) - lo, len(gr.segs)) for lo in range(0, gr.n, step)]
+        n_max = max((m * k for _, _, m, k in self.launches), default=1)
+        self.dJ = torch.zeros(self.S * n_max * self.d_out, device=dev)
+        self.norms = {(gi, oi): torch.zeros(fl.groups[gi].n, device=dev) for gi, oi, _, _ in self.outputs}
+        n_sums = sum(len(fl.groups[gi].program.outputs) for gi, _, _, _ in self.launches)
+        self.sums = torch.zeros(max(1, n_sums), device=dev)
+        self.T = torch.zeros(len(fl.term_names), device=dev)
+        coef = torch.zeros(len(fl.term_names), max(1, n_sums))
+        k = 0
+        for gi, _, _, _ in self.launches:
+            for (_, _, t, c) in fl.groups[gi].program.outputs:
+                coef[t, k] = c
+                k += 1
+        self._coef = coef.to(dev)
+
+    def _seeds_torch(self, gi, oi, J, X, dJ, lo, m):
+        """``dJ = d f_o / d J`` by autograd through the torch interpreter (the mirror of :func:`seeds`)."""
+        fl = self.fl
+        P = fl.groups[gi].program
+        dt, dev = J.dtype, J.device
+        scalars = fusion.scalar_values(fl, self.lambdas, None)
+
+        def lam(a):
+            k = fl.lam_slots[a]
+            o = fl.lam_offsets.get(k, (0, 0))[0]
+            return self.lambdas[k].detach().reshape(-1)[o + lo:o + lo + m].to(dt)
+
+        with torch.enable_grad():
+            Jg = J.detach().clone().requires_grad_(True)
+            vals = fusion.eval_group(P, m, lambda a, row, col: Jg[row, a * m:(a + 1) * m, col],
+                                     lambda a, j: X[a * m:(a + 1) * m, j],
+                                     lambda a: fl.val_arrays[a].to(dev)[lo:lo + m].to(dt), lam,
+                                     lambda a: scalars[a].detach().to(dt), dev, dt)
+            f = vals[P.outputs[oi][0]]
+            g = torch.autograd.grad(f.sum(), Jg, allow_unused=True)[0] if f.requires_grad else None
+        dJ.copy_(torch.zeros_like(J) if g is None else g)
+        return dJ
+
+    def traces(self, params=None):
+        """``T`` ``(n_terms,)`` on the device.  Two calls at the same parameters give the same bits: every
+        kernel of the chain computes each element in a fixed order and the sums run in a fixed order."""
+        from . import _lib, jet_layered
+        prog, fl = self.prog, self.fl
+        P = (prog.net.flat if params is None else params).detach().contiguous()
+        if P.dtype != torch.float32:
+            raise ValueError("the NTK trace kernels take the fp32 parameter vector")
+        gram = gram_norms if self.hip else gram_norms_torch
+        S = self.S
+        k = 0
+        for gi, lo, m, slots in self.launches:
+            gr = fl.groups[gi]
+            offs = [prog.segments[s].offset for s in gr.segs]
+            X = prog.X_all[offs[0] + lo:offs[0] + lo + m] if slots == 1 else \
+                torch.cat([prog.X_all[o + lo:o + lo + m] for o in offs], dim=0)
+            X = X.contiguous()
+            N = X.shape[0]
+            J, saved = jet_layered.forward_raw(X, P, prog.net, prog.plan, precision="fp32")
+            dJ = self.dJ[:J.numel()].view(J.shape)
+            for oi in range(len(gr.program.outputs)):
+                # slot k's instance i is point k m + (i - lo) of this launch's point list
+                if self.hip:
+                    seeds(self.fop, gi, oi, J, X, dJ, lo, m, [k_ * m - lo for k_ in range(slots)])
+                else:
+                    self._seeds_torch(gi, oi, J, X, dJ, lo, m)
+                n2 = self.norms[(gi, oi)][lo:lo + m]
+                for li, (H, Z) in enumerate(jet_layered.adjoint_planes(saved, dJ)):
+                    gram(H, Z, S, N, m, 0, m if slots == 2 else None, out=n2, accumulate=li > 0)
+                if self.hip:
+                    _lib.check(_lib.load().tdq_ntk_sum(_lib.ptr(n2), m, _lib.ptr(self.sums[k:k + 1]),
+                                                       _lib.stream_ptr(P.device)), "tdq_ntk_sum")
+                else:
+                    self.sums[k] = n2.sum()
+                k += 1
+        torch.sum(self._coef * self.sums, dim=1, out=self.T)
+        return self.T
+
+    def instance_norms(self, gi, oi):
+        """Per-instance norms of output ``oi`` of group ``gi`` from the last :meth:`traces` call."""
+        return self.norms[(gi, oi)]
+
+
 def build(prog, lambdas):
-    """The trace evaluator of a finalized program: :class:`NTKTraceOp` inside the HIP envelope, else
-    :class:`TorchNTK` (on a GPU the reason goes to ``prog.reasons`` and is warned once).  ``ValueError``
-    when the loss cannot be traced into a fused program - that program defines the outputs."""
+    """The trace evaluator of a finalized program: :class:`NTKTraceOp` inside the fused kernels' envelope,
+    :class:`LayeredNTKOp` inside the layer-wise one (:func:`layered_reason`), else :class:`TorchNTK` (on a
+    GPU the reason goes to ``prog.reasons`` and is warned once).  ``ValueError`` when the loss cannot be
+    traced into a fused program - that program defines the outputs."""
     if prog.backend not in ("hip", "jet"):
         raise ValueError("NTK adaptive weighting needs the jet path (backend 'jet' or 'hip'): "
                          + "; ".join(prog.reasons or [f"backend {prog.backend!r}"]))
@@ -345,6 +539,8 @@ def build(prog, lambdas):
         why = hip_reason(prog)
         if why is None:
             return NTKTraceOp(prog, prog.fused_op)
+        if layered_enabled() and layered_reason(prog) is None:
+            return LayeredNTKOp(prog, fl, lambdas, fop=prog.fused_op)
         from ..models.loss import _warn_once
         msg = f"NTK traces on the torch jet: {why}"
         prog.reasons.append(msg)

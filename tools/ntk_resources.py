@@ -2,6 +2,7 @@
 (``csrc/ntk_trace.hip``), compiled offline with hipcc for gfx950 with the library's flags (no GPU needed):
 
     python tools/ntk_resources.py [--out FILE]
+    python tools/ntk_resources.py --gram [--out FILE]     # ntk_gram_kernel (csrc/ntk_gram.hip) instead
 
 One line per variant: width tiles, streams, pair mode, VGPRs, AGPRs, scratch bytes per lane (spills), the
 static LDS and the dynamic LDS the launcher asks for (the wave-private adjoint images, ``4 S WT`` KiB)."""
@@ -19,8 +20,9 @@ def main():
     from tensordiffeq_amd.csrc import build
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--gram", action="store_true", help="the Gram-product kernel of the layer-wise NTK path")
     a = ap.parse_args()
-    src = os.path.join(build.HERE, "ntk_trace.hip")
+    src = os.path.join(build.HERE, "ntk_gram.hip" if a.gram else "ntk_trace.hip")
     r = subprocess.run([build.hipcc()] + build._flags() + ["--cuda-device-only", "-S", src, "-o", os.devnull,
                                                            "-Rpass-analysis=kernel-resource-usage"],
                        capture_output=True, text=True)
@@ -39,6 +41,23 @@ def main():
         elif cur is not None and ":" in t:
             key, val = t.split(":", 1)
             cur[key.strip()] = val.split("[")[0].strip()
+    if a.gram:   # one kernel: S, the widths, the load path and pair mode are run-time arguments
+        lines = ["# ntk_gram_kernel, hipcc " + " ".join(build._flags()[:3]),
+                 f"{'kernel':<16} {'VGPRs':>6} {'AGPRs':>6} {'SGPRs':>6} {'spill VGPRs':>11} {'scratch B/lane':>14} "
+                 f"{'LDS static':>10} {'occupancy':>9}"]
+        for row in rows:
+            if "ntk_gram_kernel" in row["name"]:
+                lines.append(f"{'ntk_gram_kernel':<16} {row.get('VGPRs', '?'):>6} {row.get('AGPRs', '?'):>6} "
+                             f"{row.get('TotalSGPRs', '?'):>6} {row.get('VGPRs Spill', '?'):>11} "
+                             f"{row.get('ScratchSize [bytes/lane]', '?'):>14} "
+                             f"{row.get('LDS Size [bytes/block]', '?'):>10} "
+                             f"{row.get('Occupancy [waves/SIMD]', '?'):>9}")
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     lines = ["# ntk_norm_kernel<WT, S, PAIR>, hipcc " + " ".join(build._flags()[:3]),
              f"{'WT':>3} {'S':>2} {'pair':>4} {'VGPRs':>6} {'AGPRs':>6} {'spill VGPRs':>11} {'scratch B/lane':>14} "
              f"{'LDS static':>10} {'LDS dynamic':>11}"]
