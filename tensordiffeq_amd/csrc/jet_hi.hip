@@ -1,5 +1,6 @@
-// High-order Taylor jets (any multi-index up to order 4) of a tanh MLP on SMALL point sets: fp32
-// elementwise work, split-bf16 (bf16x3) MFMA layer GEMMs, fp32 MFMA weight gradients.
+// High-order Taylor jets (any multi-index up to order 4) of a tanh MLP: fp32 elementwise work,
+// split-bf16 (bf16x3) MFMA layer GEMMs, fp32 MFMA weight gradients.  One forward kernel and one
+// adjoint-chain kernel at 4, 8 or 16 points per workgroup.
 //
 // Why a separate kernel: the fused jet kernels (jet_bf3.h) carry value, first- and second-order
 // streams only, with the post-activation identities of the order-2 tanh jet.  The reference's
@@ -21,24 +22,30 @@
 // and post-activation streams h (fp32, [layer][point x stream][feature]); order >= 3 adjoints need
 // z itself, the weight gradients need h.
 //
-// Kernels (a few hundred points: latency, not bandwidth, is the budget):
-//   * forward: workgroup = 512 threads = 4 points, thread (f, g) owns feature f of point g; one
-//     layer's weights and the points' activations in LDS, the layer GEMM on bf16x3 MFMA tiles
-//     (hi_mma: rows point x stream, wave w = 16 output columns); the next layer's weights load
-//     into registers during this layer's GEMM (zero padding applied at the LDS store, so nothing
-//     waits for them before it).
-//   * adjoint chain (same layout): zb_i = tanh-jet adjoint of hb_i, hb_{i-1} = W_i zb_i -> B.
+// Kernels:
+//   * forward <S, CH, X3, NP>: workgroup = 512 threads = HI_TG groups of 128, NP = 4 | 8 | 16 points;
+//     thread (f, g) owns feature f of the PT = NP / HI_TG local points j HI_TG + g; one layer's
+//     weights and the points' activations in LDS, the layer GEMM on bf16x3 MFMA tiles (hi_mma: rows
+//     point x stream in 16-row tiles, wave w = 16 output columns, each weight fragment fetched and
+//     split once per k-block for all row tiles); the next layer's weights load into registers during
+//     this layer's GEMM (zero padding applied at the LDS store, so nothing waits for them before it).
+//   * adjoint chain (same template, same layout): zb_i = tanh-jet adjoint of hb_i, hb_{i-1} = W_i zb_i -> B.
 //   * weight gradients: dK_i = H_{i-1}^T B_i as 32 x 32 tiles over point splits (one slab row per
 //     split); the vector parameters (biases, K0, Ko, bo) summed per workgroup by the chain itself
 //     (one vslab row per workgroup); a fixed-order sum of the rows gives the gradient
 //     (deterministic), which the fused step tail adds to theta's.
+// Per row the arithmetic does not depend on NP (k order, the three / six products, hi_sigmas, chain /
+// table code, the output layer's sum), so a row's streams are the same bits at every tile.
 // Loads are unconditional from clamped addresses (a conditional load is a branch with a wait
 // behind it).  The stream count is a template parameter, and the common plan - the
 // univariate chain u, u_v, u_vv, u_vvv(, u_vvvv) of the reference's periodic BCs - has its tanh jet
 // and adjoint as straight-line code; other plans interpret the partition table.
-// Large point sets (a residual with u_xxx / u_xxxx: every collocation point is a high-order point)
-// take the tile kernels further down (8 / 16 points per workgroup, tdq_jet_hi_tile_* entry points);
-// the three kernels and the entry points of the small sets stay as they are for every N.
+// The tiles: 4 points serve the few hundred periodic-BC points, where latency is the budget and more
+// workgroups beat fewer weight reloads.  A residual with u_xxx / u_xxxx (KdV-type) makes every
+// collocation point a high-order point, 10^4 - 10^6 of them, and bandwidth the budget: 4 points
+// reload a 64 KB layer of weights per layer for 4 points, 8 or 16 points share it (the LDS table
+// below says where they fit).  Two C entry families launch the same kernels: tdq_jet_hi_* (tile 4,
+// the small sets' scratch and splits) and tdq_jet_hi_tile_* (any tile; see the entry points).
 // History (AC-baseline, 402 points, order 4; profiles/): interpreted 256-thread first build
 // 0.31 + 0.40 ms per step; this layout 26 + 57 us isolated (profiles/r4g_kernel_stats_hi_isolated.txt);
 // MFMA layer GEMMs: chain -16 %, forward -7 % of workgroup cycles (profiles/r4x_hi_phase_stamps_mfma.txt);
@@ -53,8 +60,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define HI_MAXB 4
 #define HI_W 128
 #define HI_TG 4                      // 128-thread groups per workgroup (one feature per thread)
-#define HI_PT 1                      // points per thread
-#define HI_NP (HI_TG * HI_PT)        // points per workgroup
+#define HI_NP HI_TG                  // points per workgroup of the smallest tile (tiles: 4, 8, 16)
 #define HI_THREADS (HI_W * HI_TG)
 #define HI_WS (HI_W + 4)             // LDS row strides (float4 rows, conflict-free)
 #define HI_AS (HI_W + 4)
@@ -215,19 +221,37 @@ __device__ __forceinline__ void hi_tanh_b(const HiSpec& sp, const float (&z)[S],
     table_b<S>(sp, z, hb, zb);
 }
 
-// LDS of the forward / adjoint-chain kernels (floats, dynamic, sized per launch):
+// LDS of the forward / adjoint-chain kernels at NP points per workgroup (floats, dynamic, sized per
+// launch):
 //   W [HI_W][HI_WS]          one layer's weights (row stride 132: the 8-float MFMA fragment rows
 //                            of 16 lanes land on distinct banks)
-//   A 2 x [HI_NP][S][HI_AB]  the workgroup's activations / adjoints as MFMA A rows, split once into
+//   A 2 x [NP][S][HI_AB]     the workgroup's activations / adjoints as MFMA A rows, split once into
 //                            bf16 hi and lo at the store (every wave reads the same rows); a third
 //                            plane (lo2) for the three-way split of deep networks (HI_X3_DEPTH)
-//   R [HI_MR][HI_AS]         GEMM product (rows point * S + stream; both 16-row MFMA tiles)
+//   R [hi_rows][HI_AS]       GEMM product (rows point * S + stream, in whole 16-row MFMA tiles)
 //   V [HI_TG][nvs][HI_W]     (chain) vector-parameter partials (nvs slots, hi_nvs)
-constexpr int HI_MR = 32;  // GEMM rows: HI_NP points x at most HI_MAXS streams
+// In bytes: W 67,584 + A NP S 272 (2 | 3 planes) + R 16 ceil(NP S / 16) 528 + V 2,048 nvs (chain
+// only; nvs = hi_nvs: 3 for d_in <= 2, d_out = 1, up to 9 with several hidden layers, 17 with one).
+// Largest NP that fits HI_LDS_MAX = 163,840 (forward / chain at nvs = 3 / chain at nvs = 9):
+//
+//     S      two-term split (<= 4 hidden layers)          three-term split
+//     2, 3   16 / 16 / 16                                 16 / 16 / 16
+//     4      16 / 16 / 16  (136,192 / 142,336 / 154,624)  16 / 16 / 8  (153,600 / 159,744 / 172,032)
+//     5      16 / 16 /  8  (153,344 / 159,488 / 171,776)   8 /  8 / 8
+//     6       8 /  8 /  8                                  8 /  8 / 8
+//     7       8 /  8 /  8                                  8 /  8 / 4  (8: 147,072 / 153,216 / 165,504)
+//     8       8 /  8 /  8  (136,192 / 142,336 / 154,624)   8 /  8 / 4  (8: 153,600 / 159,744 / 172,032)
+//     NP = 4 fits everywhere: S = 8 takes 101,888 / 108,032 / 120,320 and 110,592 / 116,736 / 129,024,
+//     one hidden layer with d_in = 8, d_out = 4 (nvs = 17, two-term) 136,704
+//
+// (per instantiation, with registers and spills: profiles/r19_jet_hi_resources.txt)
+// (R aliases nothing: every area is live across a GEMM - W and A are its operands, V waits for the
+// hi_vsum after it - so there is no dead area that would buy a size.)  hi_t_fits is the test; the
+// host picks the tile of the forward and of the chain separately (ops/jet_hi.py).
 // bf16 row stride of the split A rows: 272 B = 68 words, so the 16 rows of a ds_read_b128 pass
 // (one 8-element column group) start 4 banks apart - conflict-free
 constexpr int HI_AB = 136;
-static_assert(HI_NP * HI_MAXS <= HI_MR, "two 16-row MFMA tiles cover the workgroup's rows");
+template <int NP>
 struct HiLds {
   float* W;
   float* A;
@@ -236,8 +260,8 @@ struct HiLds {
   int S;
   __device__ float& w(int k, int f) const { return W[k * HI_WS + f]; }
   __device__ __bf16* ah() const { return reinterpret_cast<__bf16*>(A); }
-  __device__ __bf16* al() const { return reinterpret_cast<__bf16*>(A) + HI_NP * S * HI_AB; }
-  __device__ __bf16* a2() const { return reinterpret_cast<__bf16*>(A) + 2 * HI_NP * S * HI_AB; }
+  __device__ __bf16* al() const { return reinterpret_cast<__bf16*>(A) + NP * S * HI_AB; }
+  __device__ __bf16* a2() const { return reinterpret_cast<__bf16*>(A) + 2 * NP * S * HI_AB; }
 };
 // The layer GEMMs' operands are split into two bf16 terms (three products, ~1e-5 per GEMM).  Each
 // GEMM's rounding is independent, so the error of a deep network grows with its depth: 16 hidden
@@ -247,20 +271,26 @@ struct HiLds {
 // reference's networks - the kernels are the two-term ones, bit for bit.
 #define HI_X3_DEPTH 4
 __host__ __device__ inline bool hi_x3(int n_hidden) { return n_hidden > HI_X3_DEPTH; }
+// GEMM rows: whole 16-row MFMA tiles over the NP S rows of the workgroup
+__host__ __device__ constexpr int hi_rows(int NP, int S) { return (NP * S + 15) / 16 * 16; }
 // floats of the A rows: two (three: x3) bf16 planes of HI_AB per row
-__host__ __device__ inline size_t hi_a_floats(int S, bool x3) { return (size_t)HI_NP * S * HI_AB * (x3 ? 3 : 2) / 2; }
-__host__ __device__ inline size_t hi_lds_floats(int S, int nvs, bool x3) {
-  return (size_t)HI_W * HI_WS + hi_a_floats(S, x3) + (size_t)HI_MR * HI_AS + (size_t)HI_TG * nvs * HI_W;
+__host__ __device__ constexpr size_t hi_a_floats(int NP, int S, bool x3) {
+  return (size_t)NP * S * HI_AB * (x3 ? 3 : 2) / 2;
 }
-__device__ inline HiLds hi_lds_map(float* base, int S, bool x3) {
-  HiLds L;
+__host__ __device__ constexpr size_t hi_lds_floats(int NP, int S, int nvs, bool x3) {
+  return (size_t)HI_W * HI_WS + hi_a_floats(NP, S, x3) + (size_t)hi_rows(NP, S) * HI_AS + (size_t)HI_TG * nvs * HI_W;
+}
+template <int NP>
+__device__ inline HiLds<NP> hi_lds_map(float* base, int S, bool x3) {
+  HiLds<NP> L;
   L.S = S;
   L.W = base;
   L.A = L.W + HI_W * HI_WS;
-  L.R = L.A + hi_a_floats(S, x3);
-  L.V = L.R + HI_MR * HI_AS;
+  L.R = L.A + hi_a_floats(NP, S, x3);
+  L.V = L.R + hi_rows(NP, S) * HI_AS;
   return L;
 }
+
 
 // Diagnostic build only (tools/hi_stamps.cpp, -DHI_STAMPS): s_memtime at phase boundaries of
 // workgroup 0, printed at the end; compiled out otherwise.
@@ -319,7 +349,8 @@ __device__ __forceinline__ void hi_get_w(HiWRegs& r, const float* __restrict__ P
     }
   }
 }
-__device__ __forceinline__ void hi_put_w(const HiLds& L, const HiWRegs& r, const NetDims& d, int layer) {
+template <int NP>
+__device__ __forceinline__ void hi_put_w(const HiLds<NP>& L, const HiWRegs& r, const NetDims& d, int layer) {
   const int win = hw(d, layer - 1), wout = hw(d, layer);
 #pragma unroll
   for (int u = 0; u < HI_WQ; ++u) {
@@ -339,7 +370,7 @@ __device__ __forceinline__ size_t hi_row(int layer, int n, int s, int S, int N) 
 
 // Layer GEMMs on bf16x3 MFMA (v_mfma_f32_16x16x32_bf16; fp32 operands split into bf16 hi + lo,
 // products hi*hi + hi*lo + lo*hi, fp32 accumulation - the split-bf16 family of the fused kernels,
-// ~1e-5 relative).  Rows m = point * S + stream (at most 32: two 16-row tiles, rows >= 4 S zero);
+// ~1e-5 relative).  Rows m = point * S + stream (16-row tiles, rows >= NP S zero);
 // wave w owns the 16 output columns [16 w, 16 w + 16).  Lane l: A[row l & 15][k = 8 (l >> 4) + j],
 // B[k][col l & 15], C[4 (l >> 4) + r][l & 15].  The product lands in R as [m][HI_AS].
 // Networks deeper than HI_X3_DEPTH take a third term per operand and the three products of the next
@@ -377,8 +408,8 @@ __device__ __forceinline__ f32x4 hi_mma3x(const hbf16x8& ah, const hbf16x8& al, 
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, bh, c, 0, 0, 0);
 }
 // element (m, k) of the A rows, split into bf16 hi + lo (hi_split's rounding)
-template <bool X3>
-__device__ __forceinline__ void hi_put_a(const HiLds& L, int m, int k, float x) {
+template <bool X3, int NP>
+__device__ __forceinline__ void hi_put_a(const HiLds<NP>& L, int m, int k, float x) {
   const __bf16 hx = (__bf16)x;
   L.ah()[m * HI_AB + k] = hx;
   const float r = x - (float)hx;
@@ -386,35 +417,25 @@ __device__ __forceinline__ void hi_put_a(const HiLds& L, int m, int k, float x) 
   L.al()[m * HI_AB + k] = lx;
   if constexpr (X3) L.a2()[m * HI_AB + k] = (__bf16)(r - (float)lx);
 }
-// A fragment (row m, columns k0 .. k0 + 7) of the workgroup, hi and lo; rows past 4 S read as zero
-__device__ __forceinline__ void hi_arow(const HiLds& L, int m, int k0, int S, hbf16x8& h, hbf16x8& lo) {
-  const bool in = m < HI_NP * S;
-  const int o = (in ? m : 0) * HI_AB + k0;
-  const hbf16x8 u = *reinterpret_cast<const hbf16x8*>(L.ah() + o), v = *reinterpret_cast<const hbf16x8*>(L.al() + o);
-  const hbf16x8 z = {};
-  h = in ? u : z;
-  lo = in ? v : z;
-}
-__device__ __forceinline__ void hi_arow2(const HiLds& L, int m, int k0, int S, hbf16x8& l2) {
-  const bool in = m < HI_NP * S;
-  const hbf16x8 u = *reinterpret_cast<const hbf16x8*>(L.a2() + (in ? m : 0) * HI_AB + k0);
-  const hbf16x8 z = {};
-  l2 = in ? u : z;
-}
+// The layer GEMM over MT = ceil(NP S / 16) row tiles: the weight fragment of a k-block is fetched and
+// split once for all of them; rows past NP S read as zero; R has 16 MT rows.
 // TRANS = false (forward): out[m][c] = sum_k A[m][k] W[k][c]; true (adjoint chain): out[m][c] =
 // sum_o A[m][o] W[c][o]
-template <bool TRANS, bool X3>
-__device__ __forceinline__ void hi_mma(const HiLds& L, int S, int kin) {
+template <bool TRANS, bool X3, int NP, int S>
+__device__ __forceinline__ void hi_mma(const HiLds<NP>& L, int kin) {
+  constexpr int MT = hi_rows(NP, S) / 16;
   const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, p = l & 15, g = l >> 4, col = 16 * wv + p;
-  f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f};  // X3: the small products
+  f32x4 c[MT], e[X3 ? MT : 1];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) c[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int mt = 0; mt < (X3 ? MT : 1); ++mt) e[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nk = (kin + 31) >> 5;
+  const hbf16x8 zero = {};
   for (int kk = 0; kk < nk; ++kk) {
     const int k0 = 32 * kk + 8 * g;
     float w[8];
-    hbf16x8 a0h, a0l, a1h, a1l, wh, wl;
-    hi_arow(L, p, k0, S, a0h, a0l);
-    hi_arow(L, 16 + p, k0, S, a1h, a1l);
+    hbf16x8 wh, wl, w2;
     if constexpr (TRANS) {
       const float* r = &L.w(col, k0);
       const f32x4 u = *reinterpret_cast<const f32x4*>(r), v = *reinterpret_cast<const f32x4*>(r + 4);
@@ -428,74 +449,86 @@ __device__ __forceinline__ void hi_mma(const HiLds& L, int S, int kin) {
       for (int j = 0; j < 8; ++j) w[j] = L.w(k0 + j, col);
     }
     hi_split(w, wh, wl);
-    c0 = hi_mma3(a0h, a0l, wh, wl, c0);
-    c1 = hi_mma3(a1h, a1l, wh, wl, c1);
-    if constexpr (X3) {
-      hbf16x8 a02, a12, w2;
-      hi_arow2(L, p, k0, S, a02);
-      hi_arow2(L, 16 + p, k0, S, a12);
-      hi_split2(w, w2);
-      e0 = hi_mma3x(a0h, a0l, a02, wh, wl, w2, e0);
-      e1 = hi_mma3x(a1h, a1l, a12, wh, wl, w2, e1);
+    if constexpr (X3) hi_split2(w, w2);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      const int m = 16 * mt + p;
+      const bool in = m < NP * S;
+      const int o = (in ? m : 0) * HI_AB + k0;
+      hbf16x8 ah = *reinterpret_cast<const hbf16x8*>(L.ah() + o), al = *reinterpret_cast<const hbf16x8*>(L.al() + o);
+      ah = in ? ah : zero;
+      al = in ? al : zero;
+      c[mt] = hi_mma3(ah, al, wh, wl, c[mt]);
+      if constexpr (X3) {
+        hbf16x8 a2 = *reinterpret_cast<const hbf16x8*>(L.a2() + o);
+        a2 = in ? a2 : zero;
+        e[mt] = hi_mma3x(ah, al, a2, wh, wl, w2, e[mt]);
+      }
     }
   }
-  if constexpr (X3) {
-    c0 += e0;
-    c1 += e1;
-  }
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    L.R[(4 * g + r) * HI_AS + col] = c0[r];
-    L.R[(16 + 4 * g + r) * HI_AS + col] = c1[r];
+  for (int mt = 0; mt < MT; ++mt) {
+    if constexpr (X3) c[mt] += e[mt];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) L.R[(16 * mt + 4 * g + r) * HI_AS + col] = c[mt][r];
   }
 }
 
-// thread t: point p = t >> 7 and feature f = t & 127 in the elementwise phases; in the GEMM, feature
-// quad f4 = (t >> 2) & 31 and k-quarter ks = t & 3 (so f = 4 f4 + ks)
-template <int S, bool CH, bool X3>
-__global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) jet_hi_fwd_kernel(const float* __restrict__ X, int N,
-                                                                const float* __restrict__ P, NetDims d, HiSpec sp,
-                                                                float* __restrict__ J, int ldJ, int j0,
-                                                                float* __restrict__ Zb, float* __restrict__ Hb) {
+
+// forward, NP points per workgroup: thread t = (feature f = t & 127, group pg = t >> 7) owns feature f
+// of the local points j HI_TG + pg, j < PT = NP / HI_TG; the GEMM is hi_mma's (wave w: columns 16 w ..)
+template <int S, bool CH, bool X3, int NP>
+__global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
+jet_hi_fwd_kernel(const float* __restrict__ X, int N, const float* __restrict__ P, NetDims d, HiSpec sp,
+                  float* __restrict__ J, int ldJ, int j0, float* __restrict__ Zb, float* __restrict__ Hb) {
+  constexpr int PT = NP / HI_TG;
+  static_assert(NP % HI_TG == 0 && NP * S <= HI_W, "the output layer's products take NP S rows of the weight area");
   extern __shared__ __attribute__((aligned(16))) float hi_lds[];
-  const HiLds L = hi_lds_map(hi_lds, S, X3);
+  const HiLds<NP> L = hi_lds_map<NP>(hi_lds, S, X3);
   HI_TS_DECL
   HI_TS()
   const int t = threadIdx.x, f = t & (HI_W - 1), pg = t >> 7;
   const int Lh = d.n_hidden;
-  const int m0 = blockIdx.x * HI_NP + pg;
-  const bool ok = m0 < N;
-  const int n = ok ? m0 : N - 1;
+  bool ok[PT];
+  int n[PT];
+#pragma unroll
+  for (int j = 0; j < PT; ++j) {
+    const int m = blockIdx.x * NP + j * HI_TG + pg;
+    ok[j] = m < N;
+    n[j] = ok[j] ? m : N - 1;
+  }
   HiWRegs wr;
   if (Lh > 1) hi_get_w(wr, P, d, 1);
-  float z[S], hl[S];  // hl: the last hidden layer's h (output layer products)
+  float z[PT][S], h[PT][S];
   {  // layer 0: z = x K0 + b0 (value), K0[var] (first order), 0 (higher)
     const int w0 = hw(d, 0);
     const int fc = f < w0 ? f : w0 - 1;
-    float xv[TDQ_MAXD], kv[TDQ_MAXD];
+    float xv[PT][TDQ_MAXD], kv[TDQ_MAXD];
 #pragma unroll
     for (int v = 0; v < TDQ_MAXD; ++v) {
       const int vc = v < d.d_in ? v : d.d_in - 1;
       kv[v] = P[vc * w0 + fc];
-      xv[v] = X[(size_t)n * d.d_in + vc];
+#pragma unroll
+      for (int j = 0; j < PT; ++j) xv[j][v] = X[(size_t)n[j] * d.d_in + vc];
     }
-    float a = P[d.d_in * w0 + fc];
+    float b0 = P[d.d_in * w0 + fc];
     __builtin_amdgcn_sched_barrier(0);  // all loads in flight first
 #pragma unroll
-    for (int v = 0; v < TDQ_MAXD; ++v) {
-      kv[v] = (v < d.d_in && f < w0) ? kv[v] : 0.f;
-      xv[v] = v < d.d_in ? xv[v] : 0.f;
-    }
-    a = f < w0 ? a : 0.f;
+    for (int v = 0; v < TDQ_MAXD; ++v) kv[v] = (v < d.d_in && f < w0) ? kv[v] : 0.f;
+    b0 = f < w0 ? b0 : 0.f;
 #pragma unroll
-    for (int v = 0; v < TDQ_MAXD; ++v) a = fmaf(xv[v], kv[v], a);
-    z[0] = a;
+    for (int j = 0; j < PT; ++j) {
+      float a = b0;
 #pragma unroll
-    for (int s = 1; s < S; ++s) {
-      float k1 = 0.f;
+      for (int v = 0; v < TDQ_MAXD; ++v) a = fmaf(v < d.d_in ? xv[j][v] : 0.f, kv[v], a);
+      z[j][0] = a;
 #pragma unroll
-      for (int v = 0; v < TDQ_MAXD; ++v) k1 = sp.var[s] == v ? kv[v] : k1;
-      z[s] = sp.order[s] == 1 ? k1 : 0.f;
+      for (int s = 1; s < S; ++s) {
+        float k1 = 0.f;
+#pragma unroll
+        for (int v = 0; v < TDQ_MAXD; ++v) k1 = sp.var[s] == v ? kv[v] : k1;
+        z[j][s] = sp.order[s] == 1 ? k1 : 0.f;
+      }
     }
   }
   if (Lh > 1) hi_put_w(L, wr, d, 1);
@@ -505,72 +538,70 @@ __global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu
     if (i >= 1) {  // z_i = h_{i-1} W_i (+ b_i); W_{i+1} loads in flight meanwhile
       if (i + 1 < Lh) hi_get_w(wr, P, d, i + 1);
       float b = P[off_layer(d, i) + hw(d, i - 1) * wi + (f < wi ? f : wi - 1)];  // masked after the GEMM
-      hi_mma<false, X3>(L, S, hw(d, i - 1));
+      hi_mma<false, X3, NP, S>(L, hw(d, i - 1));
       HI_TS()
       __syncthreads();  // z in R; every GEMM read of A / W done
       b = f < wi ? b : 0.f;
 #pragma unroll
-      for (int s = 0; s < S; ++s) z[s] = L.R[(pg * S + s) * HI_AS + f] + (s == 0 ? b : 0.f);
+      for (int j = 0; j < PT; ++j)
+#pragma unroll
+        for (int s = 0; s < S; ++s) z[j][s] = L.R[((j * HI_TG + pg) * S + s) * HI_AS + f] + (s == 0 ? b : 0.f);
       if (i + 1 < Lh) hi_put_w(L, wr, d, i + 1);
       HI_TS()
     }
-    {
-      float h[S];
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
       if (f < wi) {
-        hi_tanh_f<S, CH>(sp, z, h);
+        hi_tanh_f<S, CH>(sp, z[j], h[j]);
       } else {
 #pragma unroll
-        for (int s = 0; s < S; ++s) h[s] = 0.f;
+        for (int s = 0; s < S; ++s) h[j][s] = 0.f;
       }
-      if (ok) {
+      if (ok[j]) {
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-          Zb[hi_row(i, n, s, S, N) + f] = z[s];
-          Hb[hi_row(i, n, s, S, N) + f] = h[s];
+          Zb[hi_row(i, n[j], s, S, N) + f] = z[j][s];
+          Hb[hi_row(i, n[j], s, S, N) + f] = h[j][s];
         }
       }
 #pragma unroll
-      for (int s = 0; s < S; ++s) {
-        hi_put_a<X3>(L, pg * S + s, f, h[s]);
-        hl[s] = h[s];
-      }
+      for (int s = 0; s < S; ++s) hi_put_a<X3, NP>(L, (j * HI_TG + pg) * S + s, f, h[j][s]);
     }
     HI_TS()
     __syncthreads();  // A (and W) of the next GEMM written; R read
     HI_TS()
   }
-  // ---- output layer: u_s[q] = sum_f h_s[f] Ko[f][q] (+ bo[q] on the value stream): per-feature
-  // products into LDS (the free weight area), then one thread per (point, stream, q) sums them
+  // ---- output layer: u_s[q] = sum_f h_s[f] Ko[f][q] (+ bo[q] on the value stream), one output q at a
+  // time: per-feature products of the NP S rows into the free weight area, then one thread per
+  // (point, stream) sums them (one barrier at d_out = 1, two more per further output)
   const int wl = hw(d, Lh - 1), dout = d.d_out;
   const float* Ko = P + off_layer(d, Lh);
-  float* part = L.W;  // [p][s][q][HI_W]
-  {
-    float ko[TDQ_MAXO];
+  float* part = L.W;  // [local point][s][HI_W]
+  for (int q = 0; q < dout; ++q) {
+    const float ko = ldm(Ko + (f < wl ? f : wl - 1) * dout + q, f < wl);
 #pragma unroll
-    for (int q = 0; q < TDQ_MAXO; ++q)
-      ko[q] = ldm(Ko + (f < wl ? f : wl - 1) * dout + (q < dout ? q : dout - 1), q < dout && f < wl);
+    for (int j = 0; j < PT; ++j)
 #pragma unroll
-    for (int s = 0; s < S; ++s)
-#pragma unroll
-      for (int q = 0; q < TDQ_MAXO; ++q)
-        if (q < dout) part[((pg * S + s) * TDQ_MAXO + q) * HI_W + f] = hl[s] * ko[q];
-  }
-  __syncthreads();
-  for (int c = t; c < HI_NP * S * dout; c += blockDim.x) {
-    const int q = c % dout, s = (c / dout) % S, pp = c / (dout * S);
-    const int m = blockIdx.x * HI_NP + pp;
-    if (m >= N || sp.out[s] < 0) continue;
-    const f32x4* r = reinterpret_cast<const f32x4*>(part + ((pp * S + s) * TDQ_MAXO + q) * HI_W);
-    f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
+      for (int s = 0; s < S; ++s) part[((j * HI_TG + pg) * S + s) * HI_W + f] = h[j][s] * ko;
+    __syncthreads();
+    for (int c = t; c < NP * S; c += HI_THREADS) {
+      const int s = c % S, pp = c / S;
+      const int m = blockIdx.x * NP + pp;
+      if (m >= N || sp.out[s] < 0) continue;
+      const f32x4* r = reinterpret_cast<const f32x4*>(part + (size_t)c * HI_W);
+      f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
-    for (int k = 0; k < HI_W / 4; ++k) a4 += r[k];
-    float a = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-    if (s == 0) a += Ko[wl * dout + q];
-    J[((size_t)sp.out[s] * ldJ + j0 + m) * dout + q] = a;
+      for (int k = 0; k < HI_W / 4; ++k) a4 += r[k];
+      float a = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+      if (s == 0) a += Ko[wl * dout + q];
+      J[((size_t)sp.out[s] * ldJ + j0 + m) * dout + q] = a;
+    }
+    if (q + 1 < dout) __syncthreads();  // the next output's products overwrite part
   }
   HI_TS()
   HI_TS_PRINT("fwd")
 }
+
 
 // Per-workgroup partials of the vector parameters (hidden biases, K0, Ko, bo), written by the
 // adjoint chain (one row per workgroup, compact layout below) and summed by jet_hi_reduce_kernel:
@@ -590,7 +621,8 @@ __host__ __device__ inline int hi_nvs(const NetDims& d) {
 
 // fixed-order sum over the point groups of layer i's vector partials (slots: hi_nvs) -> the
 // workgroup's vslab row; thread (f, group g) takes slots g, g + HI_TG, ...
-__device__ __forceinline__ void hi_vsum(const HiLds& L, float* __restrict__ vrow, const NetDims& d, int i, int g,
+template <int NP>
+__device__ __forceinline__ void hi_vsum(const HiLds<NP>& L, float* __restrict__ vrow, const NetDims& d, int i, int g,
                                         int f) {
   const int Lh = d.n_hidden, din = d.d_in, dout = d.d_out, nvs = hi_nvs(d), vko = hi_vko(d);
   for (int sl = g; sl < nvs; sl += HI_TG) {
@@ -612,106 +644,133 @@ __device__ __forceinline__ void hi_vsum(const HiLds& L, float* __restrict__ vrow
   }
 }
 
-// adjoint chain: hb of the last hidden layer from dJ, then zb_i = tanh-jet adjoint, hb_{i-1} = W_i zb_i;
-// zb_i -> Bb (the hidden-to-hidden kernels' gradients are jet_hi_wgrad_kernel's); the vector
-// parameters' gradients are summed over the workgroup's points here -> vslab row blockIdx.x.
-// Thread t: point p = t >> 7, feature f = t & 127; the GEMM is hi_mma's (wave w: columns 16 w ..).
-template <int S, bool CH, bool X3>
-__global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) jet_hi_chain_kernel(int N, const float* __restrict__ P, NetDims d,
-                                                                  HiSpec sp, const float* __restrict__ X,
-                                                                  const float* __restrict__ dJ, int ldJ,
-                                                                  int j0, const float* __restrict__ Zb,
-                                                                  float* __restrict__ Bb, float* __restrict__ vslab) {
+
+// adjoint chain, NP points per workgroup (the forward's layout): hb of the last hidden layer from dJ,
+// then zb_i = tanh-jet adjoint, hb_{i-1} = W_i zb_i; zb_i -> Bb (the hidden-to-hidden kernels'
+// gradients are jet_hi_wgrad_kernel's); the vector parameters' gradients are summed over the
+// workgroup's points here (a thread sums its PT points in point order before the group sum of
+// hi_vsum) -> vslab row blockIdx.x.
+template <int S, bool CH, bool X3, int NP>
+__global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
+jet_hi_chain_kernel(int N, const float* __restrict__ P, NetDims d, HiSpec sp, const float* __restrict__ X,
+                    const float* __restrict__ dJ, int ldJ, int j0, const float* __restrict__ Zb,
+                    float* __restrict__ Bb, float* __restrict__ vslab) {
+  constexpr int PT = NP / HI_TG;
   extern __shared__ __attribute__((aligned(16))) float hi_lds[];
-  const HiLds L = hi_lds_map(hi_lds, S, X3);
+  const HiLds<NP> L = hi_lds_map<NP>(hi_lds, S, X3);
   HI_TS_DECL
   HI_TS()
   const int t = threadIdx.x, pg = t >> 7, f = t & (HI_W - 1);
   const int Lh = d.n_hidden, dout = d.d_out, din = d.d_in, nvs = hi_nvs(d);
-  const int m0 = blockIdx.x * HI_NP + pg;
-  const bool ok = m0 < N;
-  const int n = ok ? m0 : N - 1;
+  bool ok[PT];
+  int n[PT];
+#pragma unroll
+  for (int j = 0; j < PT; ++j) {
+    const int m = blockIdx.x * NP + j * HI_TG + pg;
+    ok[j] = m < N;
+    n[j] = ok[j] ? m : N - 1;
+  }
   HiWRegs wr;
   if (Lh > 1) hi_get_w(wr, P, d, Lh - 1);
   const int wl = hw(d, Lh - 1);
   const float* Ko = P + off_layer(d, Lh);
   float* vrow = vslab + (size_t)blockIdx.x * hi_vrow(d);
-  float hb[S], z[S];
-  float vo[TDQ_MAXO], vbo[TDQ_MAXO];  // Ko / bo partials of this thread's point
-  float xv[TDQ_MAXD];
+  float hb[PT][S], z[PT][S];
+  float vo[TDQ_MAXO], vbo[TDQ_MAXO];  // Ko / bo partials of this thread's points
+  // the input points (K0 partials of the last step), loaded with the loads below: a load inside the
+  // loop's exit branch makes the waitcnt pass wait for it on every iteration's GEMM (and the 8- and
+  // 16-point instances spill less with it up here: profiles/r19_jet_hi_resources.txt)
+  float xv[PT][TDQ_MAXD];
   {
     float ko[TDQ_MAXO];
 #pragma unroll
-    for (int q = 0; q < TDQ_MAXO; ++q)
-      ko[q] = ldm(Ko + (f < wl ? f : wl - 1) * dout + (q < dout ? q : dout - 1), q < dout && f < wl);
-    float u[S][TDQ_MAXO];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const int orow = sp.out[s] >= 0 ? sp.out[s] : 0;
-#pragma unroll
-      for (int q = 0; q < TDQ_MAXO; ++q) u[s][q] = dJ[((size_t)orow * ldJ + j0 + n) * dout + (q < dout ? q : 0)];
-      z[s] = Zb[hi_row(Lh - 1, n, s, S, N) + f];
-    }
-    // the input point (K0 partials of the last step; loaded here: a load inside the loop's exit
-    // branch makes the waitcnt pass wait for it on every iteration's GEMM)
-#pragma unroll
-    for (int v = 0; v < TDQ_MAXD; ++v) xv[v] = X[(size_t)n * din + (v < din ? v : din - 1)];
-    // every load above in flight before the first use (the scheduler otherwise interleaves each load
-    // with its use: one memory latency per load); masks applied after
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-#pragma unroll
-      for (int q = 0; q < TDQ_MAXO; ++q) u[s][q] = (sp.out[s] >= 0 && ok && q < dout) ? u[s][q] : 0.f;
-      z[s] = f < wl ? z[s] : 0.f;
-    }
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      float a = 0.f;
-#pragma unroll
-      for (int q = 0; q < TDQ_MAXO; ++q) a = fmaf(ko[q], u[s][q], a);
-      hb[s] = a;
-    }
-    // Ko[f][q] = sum over points and seeded streams of h_s[f] dJ_s[q]; bo[q] = sum of dJ_value[q]
-    float h[S];
-    hi_tanh_f<S, CH>(sp, z, h);
-#pragma unroll
     for (int q = 0; q < TDQ_MAXO; ++q) {
-      float a = 0.f;
+      ko[q] = ldm(Ko + (f < wl ? f : wl - 1) * dout + (q < dout ? q : dout - 1), q < dout && f < wl);
+      vo[q] = 0.f;
+      vbo[q] = 0.f;
+    }
 #pragma unroll
-      for (int s = 0; s < S; ++s) a = fmaf(f < wl ? h[s] : 0.f, u[s][q], a);
-      vo[q] = a;
-      vbo[q] = u[0][q];
+    for (int j = 0; j < PT; ++j) {
+      float u[S][TDQ_MAXO];
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const int orow = sp.out[s] >= 0 ? sp.out[s] : 0;
+#pragma unroll
+        for (int q = 0; q < TDQ_MAXO; ++q)
+          u[s][q] = dJ[((size_t)orow * ldJ + j0 + n[j]) * dout + (q < dout ? q : 0)];
+        z[j][s] = Zb[hi_row(Lh - 1, n[j], s, S, N) + f];
+      }
+#pragma unroll
+      for (int v = 0; v < TDQ_MAXD; ++v) xv[j][v] = X[(size_t)n[j] * din + (v < din ? v : din - 1)];
+      // the point's loads in flight before the first use (the scheduler otherwise interleaves each
+      // load with its use: one memory latency per load); masks applied after
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+#pragma unroll
+        for (int q = 0; q < TDQ_MAXO; ++q) u[s][q] = (sp.out[s] >= 0 && ok[j] && q < dout) ? u[s][q] : 0.f;
+        z[j][s] = f < wl ? z[j][s] : 0.f;
+      }
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        float a = 0.f;
+#pragma unroll
+        for (int q = 0; q < TDQ_MAXO; ++q) a = fmaf(ko[q], u[s][q], a);
+        hb[j][s] = a;
+      }
+      // Ko[f][q] = sum over points and seeded streams of h_s[f] dJ_s[q]; bo[q] = sum of dJ_value[q]
+      float h[S];
+      hi_tanh_f<S, CH>(sp, z[j], h);
+#pragma unroll
+      for (int q = 0; q < TDQ_MAXO; ++q) {
+        float a = 0.f;
+#pragma unroll
+        for (int s = 0; s < S; ++s) a = fmaf(f < wl ? h[s] : 0.f, u[s][q], a);
+        vo[q] += a;
+        vbo[q] += u[0][q];
+      }
     }
   }
   HI_TS()
   for (int i = Lh - 1; i >= 0; --i) {
     const int wi = hw(d, i);
     {
-      float zb[S];
-      if (f < wi) {
-        hi_tanh_b<S, CH>(sp, z, hb, zb);
-      } else {
+      // vector-parameter partials of this thread's points (padding points: zero adjoints already)
+      float vb = 0.f, vk[TDQ_MAXD];
 #pragma unroll
-        for (int s = 0; s < S; ++s) zb[s] = 0.f;
+      for (int v = 0; v < TDQ_MAXD; ++v) vk[v] = 0.f;
+#pragma unroll
+      for (int j = 0; j < PT; ++j) {
+        float zb[S];
+        if (f < wi) {
+          hi_tanh_b<S, CH>(sp, z[j], hb[j], zb);
+        } else {
+#pragma unroll
+          for (int s = 0; s < S; ++s) zb[s] = 0.f;
+        }
+        if (ok[j]) {
+#pragma unroll
+          for (int s = 0; s < S; ++s) Bb[hi_row(i, n[j], s, S, N) + f] = zb[s];
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) hi_put_a<X3, NP>(L, (j * HI_TG + pg) * S + s, f, zb[s]);
+        vb += ok[j] ? zb[0] : 0.f;
+        if (i == 0) {  // K0 partials
+#pragma unroll
+          for (int v = 0; v < TDQ_MAXD; ++v) {
+            float g = xv[j][v] * zb[0];
+#pragma unroll
+            for (int s = 1; s < S; ++s) g += (sp.order[s] == 1 && sp.var[s] == v) ? zb[s] : 0.f;
+            vk[v] += ok[j] ? g : 0.f;
+          }
+        }
       }
-      if (ok) {
-#pragma unroll
-        for (int s = 0; s < S; ++s) Bb[hi_row(i, n, s, S, N) + f] = zb[s];
-      }
-#pragma unroll
-      for (int s = 0; s < S; ++s) hi_put_a<X3>(L, pg * S + s, f, zb[s]);
-      // vector-parameter partials of this point (padding points: zero adjoints already)
       float* V = L.V + pg * nvs * HI_W;
-      V[f] = ok ? zb[0] : 0.f;
+      V[f] = vb;
       if (i == 0) {
 #pragma unroll
-        for (int v = 0; v < TDQ_MAXD; ++v) {
-          float g = xv[v] * zb[0];
-#pragma unroll
-          for (int s = 1; s < S; ++s) g += (sp.order[s] == 1 && sp.var[s] == v) ? zb[s] : 0.f;
-          if (v < din) V[(1 + v) * HI_W + f] = ok ? g : 0.f;
-        }
+        for (int v = 0; v < TDQ_MAXD; ++v)
+          if (v < din) V[(1 + v) * HI_W + f] = vk[v];
       }
       if (i == Lh - 1) {
         const int vko = hi_vko(d);
@@ -738,24 +797,27 @@ __global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu
     if (i >= 2) hi_get_w(wr, P, d, i - 1);
     const int wp = hw(d, i - 1);
 #pragma unroll
-    for (int s = 0; s < S; ++s) z[s] = Zb[hi_row(i - 1, n, s, S, N) + f];  // used (masked) after the GEMM
+    for (int j = 0; j < PT; ++j)
+#pragma unroll
+      for (int s = 0; s < S; ++s) z[j][s] = Zb[hi_row(i - 1, n[j], s, S, N) + f];  // used (masked) after the GEMM
     __builtin_amdgcn_sched_barrier(0);
-    hi_mma<true, X3>(L, S, wi);
+    hi_mma<true, X3, NP, S>(L, wi);
     HI_TS()
     __syncthreads();  // hb in R; GEMM reads of A / W done
-    {
 #pragma unroll
-      for (int s = 0; s < S; ++s) hb[s] = L.R[(pg * S + s) * HI_AS + f];
-      if (f >= wp) {
+    for (int j = 0; j < PT; ++j)
 #pragma unroll
-        for (int s = 0; s < S; ++s) hb[s] = z[s] = 0.f;
+      for (int s = 0; s < S; ++s) {
+        const float r = L.R[((j * HI_TG + pg) * S + s) * HI_AS + f];
+        hb[j][s] = f < wp ? r : 0.f;
+        z[j][s] = f < wp ? z[j][s] : 0.f;
       }
-    }
     __syncthreads();  // R, A, V reused by the next layer
     HI_TS()
   }
   HI_TS_PRINT("chain")
 }
+
 
 // Weight gradients over the point range of split blockIdx.y (one slab row per split, reduced in
 // a fixed order afterwards): dK_i = H_{i-1}^T B_i of the hidden-to-hidden layers on 32 x 32 tiles.
@@ -894,388 +956,6 @@ __global__ void __launch_bounds__(256) jet_hi_reduce_kernel(const float* __restr
     hi_vec_reduce(blockIdx.x - ntb, vslab, nwg, Vst, d, grad);
 }
 
-// ---- Large point sets (KdV-type residuals: the high-order points are the whole collocation set,
-// 10^4 - 10^6 of them; bandwidth, not latency, is the budget) ------------------------------------
-// The 4-point kernels above reload a 64 KB layer of weights per layer for 4 points.  The tile kernels
-// below serve NP = 8 or 16 points per workgroup with the same thread layout: each of the HI_TG
-// thread groups carries PT = NP / HI_TG points through the elementwise phases (local point
-// j HI_TG + group), the GEMM covers the NP S rows in 16-row MFMA tiles, and a wave fetches and
-// splits each weight fragment once per k-block for all its row tiles.  Per row the arithmetic is
-// that of the 4-point kernels (k order, the three / six products, hi_sigmas, chain / table code, the
-// output layer's sum), so a row's streams are those of the 4-point kernels bit for bit.
-//
-// LDS (bytes): W 67,584 + A NP S 272 (2 | 3 planes) + R 16 ceil(NP S / 16) 528 + V 2,048 nvs (chain
-// only; nvs = hi_nvs: 3 for d_in <= 2, d_out = 1, up to 9).  Largest NP that fits HI_LDS_MAX =
-// 163,840 (forward / chain at nvs = 3 / chain at nvs = 9):
-//
-//     S      two-term split (<= 4 hidden layers)          three-term split
-//     2, 3   16 / 16 / 16                                 16 / 16 / 16
-//     4      16 / 16 / 16  (136,192 / 142,336 / 154,624)  16 / 16 / 8  (153,600 / 159,744 / 172,032)
-//     5      16 / 16 /  8  (153,344 / 159,488 / 171,776)   8 /  8 / 8
-//     6       8 /  8 /  8                                  8 /  8 / 8
-//     7       8 /  8 /  8                                  8 /  8 / 4  (8: 147,072 / 153,216 / 165,504)
-//     8       8 /  8 /  8  (136,192 / 142,336 / 154,624)   8 /  8 / 4  (8: 153,600 / 159,744 / 172,032)
-//
-// (per instantiation, with registers and spills: profiles/r14_jet_hi_tile_resources.txt)
-// (R aliases nothing: every area is live across a GEMM - W and A are its operands, V waits for the
-// hi_vsum after it - so there is no dead area that would buy a size.)  hi_t_fits is the test; the
-// host picks the tile of the forward and of the chain separately (ops/jet_hi.py).
-template <int NP>
-struct HiLdsT : HiLds {
-  __device__ __bf16* al() const { return reinterpret_cast<__bf16*>(A) + NP * S * HI_AB; }
-  __device__ __bf16* a2() const { return reinterpret_cast<__bf16*>(A) + 2 * NP * S * HI_AB; }
-};
-__host__ __device__ constexpr int hi_t_rows(int NP, int S) { return (NP * S + 15) / 16 * 16; }
-__host__ __device__ constexpr size_t hi_t_a_floats(int NP, int S, bool x3) {
-  return (size_t)NP * S * HI_AB * (x3 ? 3 : 2) / 2;
-}
-__host__ __device__ constexpr size_t hi_t_lds_floats(int NP, int S, int nvs, bool x3) {
-  return (size_t)HI_W * HI_WS + hi_t_a_floats(NP, S, x3) + (size_t)hi_t_rows(NP, S) * HI_AS +
-         (size_t)HI_TG * nvs * HI_W;
-}
-template <int NP>
-__device__ inline HiLdsT<NP> hi_lds_map_t(float* base, int S, bool x3) {
-  HiLdsT<NP> L;
-  L.S = S;
-  L.W = base;
-  L.A = L.W + HI_W * HI_WS;
-  L.R = L.A + hi_t_a_floats(NP, S, x3);
-  L.V = L.R + hi_t_rows(NP, S) * HI_AS;
-  return L;
-}
-template <bool X3, int NP>
-__device__ __forceinline__ void hi_put_a_t(const HiLdsT<NP>& L, int m, int k, float x) {
-  const __bf16 hx = (__bf16)x;
-  L.ah()[m * HI_AB + k] = hx;
-  const float r = x - (float)hx;
-  const __bf16 lx = (__bf16)r;
-  L.al()[m * HI_AB + k] = lx;
-  if constexpr (X3) L.a2()[m * HI_AB + k] = (__bf16)(r - (float)lx);
-}
-// hi_mma over MT = ceil(NP S / 16) row tiles: the weight fragment of a k-block is fetched and split
-// once for all of them; rows past NP S read as zero; R has 16 MT rows
-template <bool TRANS, bool X3, int NP, int S>
-__device__ __forceinline__ void hi_mma_t(const HiLdsT<NP>& L, int kin) {
-  constexpr int MT = hi_t_rows(NP, S) / 16;
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, p = l & 15, g = l >> 4, col = 16 * wv + p;
-  f32x4 c[MT], e[X3 ? MT : 1];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) c[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int mt = 0; mt < (X3 ? MT : 1); ++mt) e[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nk = (kin + 31) >> 5;
-  const hbf16x8 zero = {};
-  for (int kk = 0; kk < nk; ++kk) {
-    const int k0 = 32 * kk + 8 * g;
-    float w[8];
-    hbf16x8 wh, wl, w2;
-    if constexpr (TRANS) {
-      const float* r = &L.w(col, k0);
-      const f32x4 u = *reinterpret_cast<const f32x4*>(r), v = *reinterpret_cast<const f32x4*>(r + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        w[j] = u[j];
-        w[4 + j] = v[j];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) w[j] = L.w(k0 + j, col);
-    }
-    hi_split(w, wh, wl);
-    if constexpr (X3) hi_split2(w, w2);
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      const int m = 16 * mt + p;
-      const bool in = m < NP * S;
-      const int o = (in ? m : 0) * HI_AB + k0;
-      hbf16x8 ah = *reinterpret_cast<const hbf16x8*>(L.ah() + o), al = *reinterpret_cast<const hbf16x8*>(L.al() + o);
-      ah = in ? ah : zero;
-      al = in ? al : zero;
-      c[mt] = hi_mma3(ah, al, wh, wl, c[mt]);
-      if constexpr (X3) {
-        hbf16x8 a2 = *reinterpret_cast<const hbf16x8*>(L.a2() + o);
-        a2 = in ? a2 : zero;
-        e[mt] = hi_mma3x(ah, al, a2, wh, wl, w2, e[mt]);
-      }
-    }
-  }
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    if constexpr (X3) c[mt] += e[mt];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) L.R[(16 * mt + 4 * g + r) * HI_AS + col] = c[mt][r];
-  }
-}
-
-// forward, NP points per workgroup: thread (f, group pg) owns feature f of the local points
-// j HI_TG + pg, j < PT
-template <int S, bool CH, bool X3, int NP>
-__global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
-jet_hi_fwd_tile_kernel(const float* __restrict__ X, int N, const float* __restrict__ P, NetDims d, HiSpec sp,
-                       float* __restrict__ J, int ldJ, int j0, float* __restrict__ Zb, float* __restrict__ Hb) {
-  constexpr int PT = NP / HI_TG;
-  static_assert(NP % HI_TG == 0 && NP * S <= HI_W, "the output layer's products take NP S rows of the weight area");
-  extern __shared__ __attribute__((aligned(16))) float hi_lds[];
-  const HiLdsT<NP> L = hi_lds_map_t<NP>(hi_lds, S, X3);
-  const int t = threadIdx.x, f = t & (HI_W - 1), pg = t >> 7;
-  const int Lh = d.n_hidden;
-  bool ok[PT];
-  int n[PT];
-#pragma unroll
-  for (int j = 0; j < PT; ++j) {
-    const int m = blockIdx.x * NP + j * HI_TG + pg;
-    ok[j] = m < N;
-    n[j] = ok[j] ? m : N - 1;
-  }
-  HiWRegs wr;
-  if (Lh > 1) hi_get_w(wr, P, d, 1);
-  float z[PT][S], h[PT][S];
-  {  // layer 0
-    const int w0 = hw(d, 0);
-    const int fc = f < w0 ? f : w0 - 1;
-    float xv[PT][TDQ_MAXD], kv[TDQ_MAXD];
-#pragma unroll
-    for (int v = 0; v < TDQ_MAXD; ++v) {
-      const int vc = v < d.d_in ? v : d.d_in - 1;
-      kv[v] = P[vc * w0 + fc];
-#pragma unroll
-      for (int j = 0; j < PT; ++j) xv[j][v] = X[(size_t)n[j] * d.d_in + vc];
-    }
-    float b0 = P[d.d_in * w0 + fc];
-    __builtin_amdgcn_sched_barrier(0);  // all loads in flight first
-#pragma unroll
-    for (int v = 0; v < TDQ_MAXD; ++v) kv[v] = (v < d.d_in && f < w0) ? kv[v] : 0.f;
-    b0 = f < w0 ? b0 : 0.f;
-#pragma unroll
-    for (int j = 0; j < PT; ++j) {
-      float a = b0;
-#pragma unroll
-      for (int v = 0; v < TDQ_MAXD; ++v) a = fmaf(v < d.d_in ? xv[j][v] : 0.f, kv[v], a);
-      z[j][0] = a;
-#pragma unroll
-      for (int s = 1; s < S; ++s) {
-        float k1 = 0.f;
-#pragma unroll
-        for (int v = 0; v < TDQ_MAXD; ++v) k1 = sp.var[s] == v ? kv[v] : k1;
-        z[j][s] = sp.order[s] == 1 ? k1 : 0.f;
-      }
-    }
-  }
-  if (Lh > 1) hi_put_w(L, wr, d, 1);
-  for (int i = 0; i < Lh; ++i) {
-    const int wi = hw(d, i);
-    if (i >= 1) {  // z_i = h_{i-1} W_i (+ b_i); W_{i+1} loads in flight meanwhile
-      if (i + 1 < Lh) hi_get_w(wr, P, d, i + 1);
-      float b = P[off_layer(d, i) + hw(d, i - 1) * wi + (f < wi ? f : wi - 1)];  // masked after the GEMM
-      hi_mma_t<false, X3, NP, S>(L, hw(d, i - 1));
-      __syncthreads();  // z in R; every GEMM read of A / W done
-      b = f < wi ? b : 0.f;
-#pragma unroll
-      for (int j = 0; j < PT; ++j)
-#pragma unroll
-        for (int s = 0; s < S; ++s) z[j][s] = L.R[((j * HI_TG + pg) * S + s) * HI_AS + f] + (s == 0 ? b : 0.f);
-      if (i + 1 < Lh) hi_put_w(L, wr, d, i + 1);
-    }
-#pragma unroll
-    for (int j = 0; j < PT; ++j) {
-      if (f < wi) {
-        hi_tanh_f<S, CH>(sp, z[j], h[j]);
-      } else {
-#pragma unroll
-        for (int s = 0; s < S; ++s) h[j][s] = 0.f;
-      }
-      if (ok[j]) {
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-          Zb[hi_row(i, n[j], s, S, N) + f] = z[j][s];
-          Hb[hi_row(i, n[j], s, S, N) + f] = h[j][s];
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < S; ++s) hi_put_a_t<X3, NP>(L, (j * HI_TG + pg) * S + s, f, h[j][s]);
-    }
-    __syncthreads();  // A (and W) of the next GEMM written; R read
-  }
-  // ---- output layer, one output q at a time: per-feature products of the NP S rows into the free
-  // weight area, then one thread per (point, stream) sums them (the 4-point kernel's sum)
-  const int wl = hw(d, Lh - 1), dout = d.d_out;
-  const float* Ko = P + off_layer(d, Lh);
-  float* part = L.W;  // [local point][s][HI_W]
-  for (int q = 0; q < dout; ++q) {
-    const float ko = ldm(Ko + (f < wl ? f : wl - 1) * dout + q, f < wl);
-#pragma unroll
-    for (int j = 0; j < PT; ++j)
-#pragma unroll
-      for (int s = 0; s < S; ++s) part[((j * HI_TG + pg) * S + s) * HI_W + f] = h[j][s] * ko;
-    __syncthreads();
-    for (int c = t; c < NP * S; c += HI_THREADS) {
-      const int s = c % S, pp = c / S;
-      const int m = blockIdx.x * NP + pp;
-      if (m >= N || sp.out[s] < 0) continue;
-      const f32x4* r = reinterpret_cast<const f32x4*>(part + (size_t)c * HI_W);
-      f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 8
-      for (int k = 0; k < HI_W / 4; ++k) a4 += r[k];
-      float a = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-      if (s == 0) a += Ko[wl * dout + q];
-      J[((size_t)sp.out[s] * ldJ + j0 + m) * dout + q] = a;
-    }
-    if (q + 1 < dout) __syncthreads();  // the next output's products overwrite part
-  }
-}
-
-// adjoint chain, NP points per workgroup (jet_hi_chain_kernel's layout; a thread sums the vector
-// partials of its PT points in point order before the group sum of hi_vsum) -> vslab row blockIdx.x
-template <int S, bool CH, bool X3, int NP>
-__global__ void __launch_bounds__(HI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)))
-jet_hi_chain_tile_kernel(int N, const float* __restrict__ P, NetDims d, HiSpec sp, const float* __restrict__ X,
-                         const float* __restrict__ dJ, int ldJ, int j0, const float* __restrict__ Zb,
-                         float* __restrict__ Bb, float* __restrict__ vslab) {
-  constexpr int PT = NP / HI_TG;
-  extern __shared__ __attribute__((aligned(16))) float hi_lds[];
-  const HiLdsT<NP> L = hi_lds_map_t<NP>(hi_lds, S, X3);
-  const int t = threadIdx.x, pg = t >> 7, f = t & (HI_W - 1);
-  const int Lh = d.n_hidden, dout = d.d_out, din = d.d_in, nvs = hi_nvs(d);
-  bool ok[PT];
-  int n[PT];
-#pragma unroll
-  for (int j = 0; j < PT; ++j) {
-    const int m = blockIdx.x * NP + j * HI_TG + pg;
-    ok[j] = m < N;
-    n[j] = ok[j] ? m : N - 1;
-  }
-  HiWRegs wr;
-  if (Lh > 1) hi_get_w(wr, P, d, Lh - 1);
-  const int wl = hw(d, Lh - 1);
-  const float* Ko = P + off_layer(d, Lh);
-  float* vrow = vslab + (size_t)blockIdx.x * hi_vrow(d);
-  float hb[PT][S], z[PT][S];
-  float vo[TDQ_MAXO], vbo[TDQ_MAXO];  // Ko / bo partials of this thread's points
-  {
-    float ko[TDQ_MAXO];
-#pragma unroll
-    for (int q = 0; q < TDQ_MAXO; ++q) {
-      ko[q] = ldm(Ko + (f < wl ? f : wl - 1) * dout + (q < dout ? q : dout - 1), q < dout && f < wl);
-      vo[q] = 0.f;
-      vbo[q] = 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < PT; ++j) {
-      float u[S][TDQ_MAXO];
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const int orow = sp.out[s] >= 0 ? sp.out[s] : 0;
-#pragma unroll
-        for (int q = 0; q < TDQ_MAXO; ++q)
-          u[s][q] = dJ[((size_t)orow * ldJ + j0 + n[j]) * dout + (q < dout ? q : 0)];
-        z[j][s] = Zb[hi_row(Lh - 1, n[j], s, S, N) + f];
-      }
-      __builtin_amdgcn_sched_barrier(0);  // the point's loads in flight before the first use
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-#pragma unroll
-        for (int q = 0; q < TDQ_MAXO; ++q) u[s][q] = (sp.out[s] >= 0 && ok[j] && q < dout) ? u[s][q] : 0.f;
-        z[j][s] = f < wl ? z[j][s] : 0.f;
-      }
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        float a = 0.f;
-#pragma unroll
-        for (int q = 0; q < TDQ_MAXO; ++q) a = fmaf(ko[q], u[s][q], a);
-        hb[j][s] = a;
-      }
-      float h[S];
-      hi_tanh_f<S, CH>(sp, z[j], h);
-#pragma unroll
-      for (int q = 0; q < TDQ_MAXO; ++q) {
-        float a = 0.f;
-#pragma unroll
-        for (int s = 0; s < S; ++s) a = fmaf(f < wl ? h[s] : 0.f, u[s][q], a);
-        vo[q] += a;
-        vbo[q] += u[0][q];
-      }
-    }
-  }
-  for (int i = Lh - 1; i >= 0; --i) {
-    const int wi = hw(d, i);
-    {
-      float vb = 0.f, vk[TDQ_MAXD];
-#pragma unroll
-      for (int v = 0; v < TDQ_MAXD; ++v) vk[v] = 0.f;
-#pragma unroll
-      for (int j = 0; j < PT; ++j) {
-        float zb[S];
-        if (f < wi) {
-          hi_tanh_b<S, CH>(sp, z[j], hb[j], zb);
-        } else {
-#pragma unroll
-          for (int s = 0; s < S; ++s) zb[s] = 0.f;
-        }
-        if (ok[j]) {
-#pragma unroll
-          for (int s = 0; s < S; ++s) Bb[hi_row(i, n[j], s, S, N) + f] = zb[s];
-        }
-#pragma unroll
-        for (int s = 0; s < S; ++s) hi_put_a_t<X3, NP>(L, (j * HI_TG + pg) * S + s, f, zb[s]);
-        vb += ok[j] ? zb[0] : 0.f;
-        if (i == 0) {  // K0 partials: the input point (once per workgroup)
-#pragma unroll
-          for (int v = 0; v < TDQ_MAXD; ++v) {
-            const float xv = X[(size_t)n[j] * din + (v < din ? v : din - 1)];
-            float g = xv * zb[0];
-#pragma unroll
-            for (int s = 1; s < S; ++s) g += (sp.order[s] == 1 && sp.var[s] == v) ? zb[s] : 0.f;
-            vk[v] += ok[j] ? g : 0.f;
-          }
-        }
-      }
-      float* V = L.V + pg * nvs * HI_W;
-      V[f] = vb;
-      if (i == 0) {
-#pragma unroll
-        for (int v = 0; v < TDQ_MAXD; ++v)
-          if (v < din) V[(1 + v) * HI_W + f] = vk[v];
-      }
-      if (i == Lh - 1) {
-        const int vko = hi_vko(d);
-#pragma unroll
-        for (int q = 0; q < TDQ_MAXO; ++q) {
-          if (q >= dout) break;
-          V[(vko + q) * HI_W + f] = vo[q];
-          V[(vko + dout + q) * HI_W + f] = vbo[q];
-        }
-      }
-    }
-    if (i == 0) {
-      __syncthreads();
-      hi_vsum(L, vrow, d, i, pg, f);
-      break;
-    }
-    // hb_{i-1}[k] = sum_o zb_i[o] W_i[k][o]; the next pre-activations load meanwhile
-    hi_put_w(L, wr, d, i);
-    __syncthreads();
-    hi_vsum(L, vrow, d, i, pg, f);
-    if (i >= 2) hi_get_w(wr, P, d, i - 1);
-    const int wp = hw(d, i - 1);
-#pragma unroll
-    for (int j = 0; j < PT; ++j)
-#pragma unroll
-      for (int s = 0; s < S; ++s) z[j][s] = Zb[hi_row(i - 1, n[j], s, S, N) + f];  // used (masked) after the GEMM
-    __builtin_amdgcn_sched_barrier(0);
-    hi_mma_t<true, X3, NP, S>(L, wi);
-    __syncthreads();  // hb in R; GEMM reads of A / W done
-#pragma unroll
-    for (int j = 0; j < PT; ++j)
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const float r = L.R[((j * HI_TG + pg) * S + s) * HI_AS + f];
-        hb[j][s] = f < wp ? r : 0.f;
-        z[j][s] = f < wp ? z[j][s] : 0.f;
-      }
-    __syncthreads();  // R, A, V reused by the next layer
-  }
-}
-
 namespace {
 
 // spec_i: [S, order[S], var[S], out[S], n_terms, (stream, k, nb, b0, b1, b2, b3) x n_terms]
@@ -1334,66 +1014,85 @@ void hi_attr(K* kern) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)HI_LDS_MAX);
 }
-bool hi_lds_fits(int S, const NetDims& d) {
-  return hi_lds_floats(S, hi_nvs(d), hi_x3(d.n_hidden)) * sizeof(float) <= HI_LDS_MAX;
+// tile = points per workgroup: HI_NP (4), 8 or 16.  Whether `tile` serves S streams on this geometry
+// (chain: the adjoint chain, with its V area; else the forward)
+bool hi_t_fits(int tile, int S, const NetDims& d, bool chain) {
+  if (tile != HI_NP && tile != 8 && tile != 16) return false;
+  if (tile * S > HI_W) return false;
+  return hi_lds_floats(tile, S, chain ? hi_nvs(d) : 0, hi_x3(d.n_hidden)) * sizeof(float) <= HI_LDS_MAX;
+}
+// instantiations no network can launch (LDS at the smallest V area, hi_nvs >= 3) are left out
+constexpr bool hi_t_any(int NP, int S, bool x3, int nvs) {
+  return NP * S <= HI_W && hi_lds_floats(NP, S, nvs, x3) * sizeof(float) <= HI_LDS_MAX;
 }
 
-int hi_splits(int N) { return std::min(HI_KS, std::max(1, (N + 63) / 64)); }
-
-template <int S, bool CH, bool X3>
+template <int S, bool CH, bool X3, int NP>
 int hi_launch_fwd(const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp, float* J, int ldJ, int j0,
                   float* Zb, float* Hb, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    hi_attr(&jet_hi_fwd_kernel<S, CH, X3>);
-    attr = true;
+  if constexpr (!hi_t_any(NP, S, X3, 0)) {
+    return (int)hipErrorInvalidValue;
+  } else {
+    static bool attr = false;
+    if (!attr) {
+      hi_attr(&jet_hi_fwd_kernel<S, CH, X3, NP>);
+      attr = true;
+    }
+    hipLaunchKernelGGL((jet_hi_fwd_kernel<S, CH, X3, NP>), dim3((N + NP - 1) / NP), dim3(HI_THREADS),
+                       hi_lds_floats(NP, S, 0, X3) * sizeof(float), st, X, N, P, d, sp, J, ldJ, j0, Zb, Hb);
+    TDQ_CHECK_LAUNCH();
+    return 0;
   }
-  hipLaunchKernelGGL((jet_hi_fwd_kernel<S, CH, X3>), dim3((N + HI_NP - 1) / HI_NP), dim3(HI_THREADS),
-                     hi_lds_floats(S, 0, X3) * sizeof(float), st,
-                     X, N, P, d, sp, J, ldJ, j0, Zb, Hb);
-  TDQ_CHECK_LAUNCH();
-  return 0;
 }
 
-template <int S, bool CH, bool X3>
+template <int S, bool CH, bool X3, int NP>
 int hi_launch_chain(int N, const float* P, const NetDims& d, const HiSpec& sp, const float* X, const float* dJ,
                     int ldJ, int j0, const float* Zb, float* Bb, float* vslab, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    hi_attr(&jet_hi_chain_kernel<S, CH, X3>);
-    attr = true;
+  if constexpr (!hi_t_any(NP, S, X3, 3)) {
+    return (int)hipErrorInvalidValue;
+  } else {
+    static bool attr = false;
+    if (!attr) {
+      hi_attr(&jet_hi_chain_kernel<S, CH, X3, NP>);
+      attr = true;
+    }
+    hipLaunchKernelGGL((jet_hi_chain_kernel<S, CH, X3, NP>), dim3((N + NP - 1) / NP), dim3(HI_THREADS),
+                       hi_lds_floats(NP, S, hi_nvs(d), X3) * sizeof(float), st, N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb,
+                       vslab);
+    TDQ_CHECK_LAUNCH();
+    return 0;
   }
-  hipLaunchKernelGGL((jet_hi_chain_kernel<S, CH, X3>), dim3((N + HI_NP - 1) / HI_NP), dim3(HI_THREADS),
-                     hi_lds_floats(S, hi_nvs(d), X3) * sizeof(float), st, N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab);
-  TDQ_CHECK_LAUNCH();
-  return 0;
 }
 
-// (S, chain) -> instantiation
+// (S, chain) -> instantiation, at each tile
 #define HI_CASES(X)                                                                                           \
   X(2, true) X(3, true) X(4, true) X(5, true) X(2, false) X(3, false) X(4, false) X(5, false) X(6, false) \
       X(7, false) X(8, false)
+#define HI_TILES(X, SS, CC) X(SS, CC, 4) X(SS, CC, 8) X(SS, CC, 16)
 
-int hi_fwd(const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp, float* J, int ldJ, int j0,
-           float* Zb, float* Hb, hipStream_t st) {
+int hi_fwd(int tile, const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp, float* J, int ldJ,
+           int j0, float* Zb, float* Hb, hipStream_t st) {
   const bool ch = sp.chain != 0, x3 = hi_x3(d.n_hidden);
-#define HI_F(SS, CC)                                                                                  \
-  if (sp.S == SS && ch == CC)                                                                         \
-    return x3 ? hi_launch_fwd<SS, CC, true>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st)                   \
-              : hi_launch_fwd<SS, CC, false>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st);
-  HI_CASES(HI_F)
+#define HI_F(SS, CC, NP)                                                                              \
+  if (sp.S == SS && ch == CC && tile == NP)                                                           \
+    return x3 ? hi_launch_fwd<SS, CC, true, NP>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st)               \
+              : hi_launch_fwd<SS, CC, false, NP>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st);
+#define HI_FT(SS, CC) HI_TILES(HI_F, SS, CC)
+  HI_CASES(HI_FT)
+#undef HI_FT
 #undef HI_F
   return (int)hipErrorInvalidValue;
 }
 
-int hi_chain(int N, const float* P, const NetDims& d, const HiSpec& sp, const float* X, const float* dJ, int ldJ,
-             int j0, const float* Zb, float* Bb, float* vslab, hipStream_t st) {
+int hi_chain(int tile, int N, const float* P, const NetDims& d, const HiSpec& sp, const float* X, const float* dJ,
+             int ldJ, int j0, const float* Zb, float* Bb, float* vslab, hipStream_t st) {
   const bool ch = sp.chain != 0, x3 = hi_x3(d.n_hidden);
-#define HI_B(SS, CC)                                                                                  \
-  if (sp.S == SS && ch == CC)                                                                         \
-    return x3 ? hi_launch_chain<SS, CC, true>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st)         \
-              : hi_launch_chain<SS, CC, false>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st);
-  HI_CASES(HI_B)
+#define HI_B(SS, CC, NP)                                                                              \
+  if (sp.S == SS && ch == CC && tile == NP)                                                           \
+    return x3 ? hi_launch_chain<SS, CC, true, NP>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st)     \
+              : hi_launch_chain<SS, CC, false, NP>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st);
+#define HI_BT(SS, CC) HI_TILES(HI_B, SS, CC)
+  HI_CASES(HI_BT)
+#undef HI_BT
 #undef HI_B
   return (int)hipErrorInvalidValue;
 }
@@ -1408,94 +1107,47 @@ int hi_wgrad(int N, const NetDims& d, const HiSpec& sp, const float* Hb, const f
   return 0;
 }
 
-// one activation-sized scratch buffer (Z, H or B), in floats
-size_t hi_act_floats(int N, int n_hidden) { return (size_t)n_hidden * N * HI_MAXS * HI_W; }
+// The backward of both entry families: the adjoint chain at `tile` points per workgroup, then the weight
+// gradients over `ks` point splits into slab rows in `work` and the fixed-order reduction (deterministic).
+// A: floats of one activation buffer (Z | H | B); part: 0 = all, 1 = the chain only, 2 = the rest only.
+int hi_bwd(int tile, int ks, size_t A, const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp,
+           const float* dJ, int ldJ, int j0, float* Z, float* work, float* grad, int part, hipStream_t st) {
+  const int Ptot = param_count(d), Pst = slab_stride(Ptot);
+  if (N <= 0) return (int)hipMemsetAsync(grad, 0, sizeof(float) * Ptot, st);
+  const int nwg = (N + tile - 1) / tile;
+  float* vslab = work + (size_t)ks * Pst;
+  if (part != 2) {
+    const int rc = hi_chain(tile, N, P, d, sp, X, dJ, ldJ, j0, Z, Z + 2 * A, vslab, st);
+    if (rc || part == 1) return rc;
+  }
+  const int rc = hi_wgrad(N, d, sp, Z + A, Z + 2 * A, work, Pst, ks, st);
+  if (rc) return rc;
+  const int ntile = off_layer(d, d.n_hidden) - off_layer(d, 1);
+  const int ntb = (ntile + 255) / 256;
+  const int ncol = (d.n_hidden + d.d_in) * HI_W + HI_W * TDQ_MAXO + TDQ_MAXO;
+  hipLaunchKernelGGL(jet_hi_reduce_kernel, dim3(ntb + (ncol + 3) / 4), dim3(256), 0, st, work, ks, Pst, vslab, nwg,
+                     hi_vrow(d), ntb, d, grad);
+  TDQ_CHECK_LAUNCH();
+  return 0;
+}
 
-// ---- tile entry points (large point sets): tile = points per workgroup, 4 (the kernels above) | 8 | 16
-// weight-gradient splits grow with the point count (one slab row each; a split of 256 points is a
-// handful of staging batches), up to HI_KS_MAX rows for the serial sum of hi_tile_reduce
+// The two entry families differ in scratch and splits, not in kernels.  Small sets (tdq_jet_hi_*):
+// tile HI_NP, activation buffers sized by HI_MAXS streams, a weight-gradient split per 64 points, at
+// most HI_KS.  Large sets (tdq_jet_hi_tile_*): the caller's tile, buffers sized by the plan's S, a
+// split per 256 points (a handful of staging batches), up to HI_KS_MAX rows for the serial sum of
+// hi_tile_reduce.  The split count fixes the gradient's summation order.
+size_t hi_act_floats(int N, int n_hidden) { return (size_t)n_hidden * N * HI_MAXS * HI_W; }
+int hi_splits(int N) { return std::min(HI_KS, std::max(1, (N + 63) / 64)); }
 constexpr int HI_KS_MAX = 64;
 constexpr int HI_T_NMAX = 1 << 27;  // N S and the workgroup counts stay in int
-int hi_t_splits(int N) { return std::min(HI_KS_MAX, std::max(1, (N + 255) / 256)); }
 size_t hi_t_act_floats(int N, int n_hidden, int S) { return (size_t)n_hidden * N * S * HI_W; }
-bool hi_t_fits(int tile, int S, const NetDims& d, bool chain) {
-  if (tile == HI_NP) return hi_lds_fits(S, d);
-  if (tile != 8 && tile != 16) return false;
-  if (tile * S > HI_W) return false;
-  return hi_t_lds_floats(tile, S, chain ? hi_nvs(d) : 0, hi_x3(d.n_hidden)) * sizeof(float) <= HI_LDS_MAX;
-}
-// instantiations no network can launch (LDS at the smallest V area, hi_nvs >= 3) are left out
-constexpr bool hi_t_any(int NP, int S, bool x3, int nvs) {
-  return NP * S <= HI_W && hi_t_lds_floats(NP, S, nvs, x3) * sizeof(float) <= HI_LDS_MAX;
-}
-
-template <int S, bool CH, bool X3, int NP>
-int hi_launch_fwd_t(const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp, float* J, int ldJ,
-                    int j0, float* Zb, float* Hb, hipStream_t st) {
-  if constexpr (!hi_t_any(NP, S, X3, 0)) {
-    return (int)hipErrorInvalidValue;
-  } else {
-    static bool attr = false;
-    if (!attr) {
-      hi_attr(&jet_hi_fwd_tile_kernel<S, CH, X3, NP>);
-      attr = true;
-    }
-    hipLaunchKernelGGL((jet_hi_fwd_tile_kernel<S, CH, X3, NP>), dim3((N + NP - 1) / NP), dim3(HI_THREADS),
-                       hi_t_lds_floats(NP, S, 0, X3) * sizeof(float), st, X, N, P, d, sp, J, ldJ, j0, Zb, Hb);
-    TDQ_CHECK_LAUNCH();
-    return 0;
-  }
-}
-
-template <int S, bool CH, bool X3, int NP>
-int hi_launch_chain_t(int N, const float* P, const NetDims& d, const HiSpec& sp, const float* X, const float* dJ,
-                      int ldJ, int j0, const float* Zb, float* Bb, float* vslab, hipStream_t st) {
-  if constexpr (!hi_t_any(NP, S, X3, 3)) {
-    return (int)hipErrorInvalidValue;
-  } else {
-    static bool attr = false;
-    if (!attr) {
-      hi_attr(&jet_hi_chain_tile_kernel<S, CH, X3, NP>);
-      attr = true;
-    }
-    hipLaunchKernelGGL((jet_hi_chain_tile_kernel<S, CH, X3, NP>), dim3((N + NP - 1) / NP), dim3(HI_THREADS),
-                       hi_t_lds_floats(NP, S, hi_nvs(d), X3) * sizeof(float), st, N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb,
-                       vslab);
-    TDQ_CHECK_LAUNCH();
-    return 0;
-  }
-}
-
-template <int NP>
-int hi_fwd_t(const float* X, int N, const float* P, const NetDims& d, const HiSpec& sp, float* J, int ldJ, int j0,
-             float* Zb, float* Hb, hipStream_t st) {
-  const bool ch = sp.chain != 0, x3 = hi_x3(d.n_hidden);
-#define HI_F(SS, CC)                                                                                  \
-  if (sp.S == SS && ch == CC)                                                                         \
-    return x3 ? hi_launch_fwd_t<SS, CC, true, NP>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st)             \
-              : hi_launch_fwd_t<SS, CC, false, NP>(X, N, P, d, sp, J, ldJ, j0, Zb, Hb, st);
-  HI_CASES(HI_F)
-#undef HI_F
-  return (int)hipErrorInvalidValue;
-}
-
-template <int NP>
-int hi_chain_t(int N, const float* P, const NetDims& d, const HiSpec& sp, const float* X, const float* dJ, int ldJ,
-               int j0, const float* Zb, float* Bb, float* vslab, hipStream_t st) {
-  const bool ch = sp.chain != 0, x3 = hi_x3(d.n_hidden);
-#define HI_B(SS, CC)                                                                                  \
-  if (sp.S == SS && ch == CC)                                                                         \
-    return x3 ? hi_launch_chain_t<SS, CC, true, NP>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st)   \
-              : hi_launch_chain_t<SS, CC, false, NP>(N, P, d, sp, X, dJ, ldJ, j0, Zb, Bb, vslab, st);
-  HI_CASES(HI_B)
-#undef HI_B
-  return (int)hipErrorInvalidValue;
-}
+int hi_t_splits(int N) { return std::min(HI_KS_MAX, std::max(1, (N + 255) / 256)); }
 
 }  // namespace
 
 extern "C" {
 
+// ---- small sets: 4 points per workgroup
 // Z | H | B: pre-activations, post-activations and pre-activation adjoints of every hidden layer
 int64_t tdq_jet_hi_scratch_floats(int N, int n_hidden) { return 3 * (int64_t)hi_act_floats(N, n_hidden); }
 
@@ -1514,15 +1166,13 @@ int tdq_jet_hi_fwd(const float* X, int N, const float* P, int d_in, const int* w
   if (N <= 0) return 0;
   NetDims d;
   HiSpec sp;
-  if (!hi_dims(d, d_in, widths, d_out, n_hidden) || !hi_spec(sp, spec_i, spec_c) || !hi_lds_fits(sp.S, d))
+  if (!hi_dims(d, d_in, widths, d_out, n_hidden) || !hi_spec(sp, spec_i, spec_c) || !hi_t_fits(HI_NP, sp.S, d, true))
     return (int)hipErrorInvalidValue;
   const size_t A = hi_act_floats(N, n_hidden);
-  return hi_fwd(X, N, P, d, sp, J, ldJ, j0, Z, Z + A, reinterpret_cast<hipStream_t>(stream));
+  return hi_fwd(HI_NP, X, N, P, d, sp, J, ldJ, j0, Z, Z + A, reinterpret_cast<hipStream_t>(stream));
 }
 
 // backward: the adjoints dJ of the streams with out[s] >= 0 -> the flat parameter gradient `grad`
-// (adjoint chain per point group, then the weight gradients over point splits into slab rows in
-// `work`, reduced in a fixed order: deterministic)
 // part: 0 = all, 1 = the adjoint chain only, 2 = the weight-gradient tiles + reduction only (after a
 // part-1 call on the same buffers; the two halves may run on different streams, fit.run_ranges)
 int tdq_jet_hi_bwd_part(const float* X, int N, const float* P, int d_in, const int* widths, int d_out, int n_hidden,
@@ -1530,27 +1180,10 @@ int tdq_jet_hi_bwd_part(const float* X, int N, const float* P, int d_in, const i
                         float* work, float* grad, int part, void* stream) {
   NetDims d;
   HiSpec sp;
-  if (!hi_dims(d, d_in, widths, d_out, n_hidden) || !hi_spec(sp, spec_i, spec_c) || !hi_lds_fits(sp.S, d))
+  if (!hi_dims(d, d_in, widths, d_out, n_hidden) || !hi_spec(sp, spec_i, spec_c) || !hi_t_fits(HI_NP, sp.S, d, true))
     return (int)hipErrorInvalidValue;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int Ptot = param_count(d), Pst = slab_stride(Ptot);
-  if (N <= 0) return (int)hipMemsetAsync(grad, 0, sizeof(float) * Ptot, st);
-  const size_t A = hi_act_floats(N, n_hidden);
-  const int ks = hi_splits(N), nwg = (N + HI_NP - 1) / HI_NP;
-  float* vslab = work + (size_t)ks * Pst;
-  if (part != 2) {
-    const int rc = hi_chain(N, P, d, sp, X, dJ, ldJ, j0, Z, Z + 2 * A, vslab, st);
-    if (rc || part == 1) return rc;
-  }
-  const int rc = hi_wgrad(N, d, sp, Z + A, Z + 2 * A, work, Pst, ks, st);
-  if (rc) return rc;
-  const int ntile = off_layer(d, n_hidden) - off_layer(d, 1);
-  const int ntb = (ntile + 255) / 256;
-  const int ncol = (n_hidden + d_in) * HI_W + HI_W * TDQ_MAXO + TDQ_MAXO;
-  hipLaunchKernelGGL(jet_hi_reduce_kernel, dim3(ntb + (ncol + 3) / 4), dim3(256), 0, st, work, ks, Pst, vslab, nwg,
-                     hi_vrow(d), ntb, d, grad);
-  TDQ_CHECK_LAUNCH();
-  return 0;
+  return hi_bwd(HI_NP, hi_splits(N), hi_act_floats(N, n_hidden), X, N, P, d, sp, dJ, ldJ, j0, Z, work, grad, part,
+                reinterpret_cast<hipStream_t>(stream));
 }
 
 int tdq_jet_hi_bwd(const float* X, int N, const float* P, int d_in, const int* widths, int d_out, int n_hidden,
@@ -1566,11 +1199,10 @@ int tdq_jet_hi_lds_ok(int S, int d_in, int d_out, int n_hidden) {
   d.d_in = d_in;
   d.d_out = d_out;
   d.n_hidden = n_hidden;
-  return S >= 1 && S <= HI_MAXS && d_in <= TDQ_MAXD && d_out <= TDQ_MAXO && hi_lds_fits(S, d) ? 1 : 0;
+  return S >= 1 && S <= HI_MAXS && d_in <= TDQ_MAXD && d_out <= TDQ_MAXO && hi_t_fits(HI_NP, S, d, true) ? 1 : 0;
 }
 
-// ---- tile entry points: `tile` points per workgroup (4: the kernels of the entry points above; 8 |
-// 16: the tile kernels), scratch sized by the plan's S, weight-gradient splits growing with N
+// ---- large sets: `tile` points per workgroup (4 | 8 | 16)
 
 // whether `tile` serves S streams on this geometry: chain = 0 the forward, 1 the adjoint chain
 int tdq_jet_hi_tile_ok(int tile, int S, int d_in, int d_out, int n_hidden, int chain) {
@@ -1609,10 +1241,7 @@ int tdq_jet_hi_tile_fwd(const float* X, int N, const float* P, int d_in, const i
     return (int)hipErrorInvalidValue;
   if (N <= 0) return 0;
   const size_t A = hi_t_act_floats(N, n_hidden, sp.S);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (tile == 8) return hi_fwd_t<8>(X, N, P, d, sp, J, ldJ, j0, Z, Z + A, st);
-  if (tile == 16) return hi_fwd_t<16>(X, N, P, d, sp, J, ldJ, j0, Z, Z + A, st);
-  return hi_fwd(X, N, P, d, sp, J, ldJ, j0, Z, Z + A, st);
+  return hi_fwd(tile, X, N, P, d, sp, J, ldJ, j0, Z, Z + A, reinterpret_cast<hipStream_t>(stream));
 }
 
 // part as in tdq_jet_hi_bwd_part; `tile` is the chain's (the vector slab's row count follows it)
@@ -1624,27 +1253,8 @@ int tdq_jet_hi_tile_bwd_part(const float* X, int N, const float* P, int d_in, co
   if (!hi_dims(d, d_in, widths, d_out, n_hidden) || !hi_spec(sp, spec_i, spec_c) || !hi_t_fits(tile, sp.S, d, true) ||
       N > HI_T_NMAX || part < 0 || part > 2)
     return (int)hipErrorInvalidValue;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int Ptot = param_count(d), Pst = slab_stride(Ptot);
-  if (N <= 0) return (int)hipMemsetAsync(grad, 0, sizeof(float) * Ptot, st);
-  const size_t A = hi_t_act_floats(N, n_hidden, sp.S);
-  const int ks = hi_t_splits(N), nwg = (N + tile - 1) / tile;
-  float* vslab = work + (size_t)ks * Pst;
-  if (part != 2) {
-    const int rc = tile == 8    ? hi_chain_t<8>(N, P, d, sp, X, dJ, ldJ, j0, Z, Z + 2 * A, vslab, st)
-                   : tile == 16 ? hi_chain_t<16>(N, P, d, sp, X, dJ, ldJ, j0, Z, Z + 2 * A, vslab, st)
-                                : hi_chain(N, P, d, sp, X, dJ, ldJ, j0, Z, Z + 2 * A, vslab, st);
-    if (rc || part == 1) return rc;
-  }
-  const int rc = hi_wgrad(N, d, sp, Z + A, Z + 2 * A, work, Pst, ks, st);
-  if (rc) return rc;
-  const int ntile = off_layer(d, n_hidden) - off_layer(d, 1);
-  const int ntb = (ntile + 255) / 256;
-  const int ncol = (n_hidden + d_in) * HI_W + HI_W * TDQ_MAXO + TDQ_MAXO;
-  hipLaunchKernelGGL(jet_hi_reduce_kernel, dim3(ntb + (ncol + 3) / 4), dim3(256), 0, st, work, ks, Pst, vslab, nwg,
-                     hi_vrow(d), ntb, d, grad);
-  TDQ_CHECK_LAUNCH();
-  return 0;
+  return hi_bwd(tile, hi_t_splits(N), hi_t_act_floats(N, n_hidden, sp.S), X, N, P, d, sp, dJ, ldJ, j0, Z, work, grad,
+                part, reinterpret_cast<hipStream_t>(stream));
 }
 
 int tdq_jet_hi_limits(int* out) {

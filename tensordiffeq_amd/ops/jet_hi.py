@@ -9,9 +9,10 @@ loss the parameter gradient of their adjoints, which the fused step tail adds to
 
 A residual that itself takes a third or fourth derivative (KdV u_xxx, Kuramoto-Sivashinsky and beam
 u_xxxx) makes every collocation point a high-order point: the same composition, with ``n_hi`` in the
-tens of thousands.  For those sets the kernels have a tile variant (8 or 16 points per workgroup
-instead of 4, scratch sized by the plan's stream count, weight-gradient splits that grow with the
-point count; ``HiJetOp(tile=)``, ``AUTO_TILE_N``).
+tens of thousands.  The same kernel pair (``jet_hi_fwd_kernel`` / ``jet_hi_chain_kernel``) serves
+both at 4, 8 or 16 points per workgroup; the large sets go through the tile entry points
+(``tdq_jet_hi_tile_*``: scratch sized by the plan's stream count, weight-gradient splits that grow
+with the point count; ``HiJetOp(tile=)``, ``AUTO_TILE_N``).
 
 Stream table (``spec_i`` / ``spec_c``): the high-order plan's streams in canonical order with their
 order / variable / output row, then the Faa di Bruno terms of every stream
@@ -28,10 +29,10 @@ from ..jet import faa_terms
 
 MAX_S, MAX_T, MAX_W = 8, 48, 128
 
-# Points per workgroup.  The 4-point kernels were written for a few hundred boundary points; from
-# AUTO_TILE_N points on (a KdV-type residual: the high-order points are the collocation set) the tile
-# kernels serve 8 points per workgroup where that fits their LDS.  Below SMALL_N points ``tile=None``
-# always means the 4-point entry points, so every shape of before keeps its kernels.
+# Points per workgroup.  Tile 4 is for a few hundred boundary points; from AUTO_TILE_N points on (a
+# KdV-type residual: the high-order points are the collocation set) the kernels serve 8 points per
+# workgroup where that fits their LDS.  Below SMALL_N points ``tile=None`` always means the 4-point
+# entry points (``tdq_jet_hi_*``), so every shape of before keeps its tile, scratch and splits.
 # KdV Adam step on MI355X, bf16x3, tile 4 / 8 / 16 (profiles/r14_jet_hi_tile_sweep.jsonl; run range
 # 0.03 ms): 2,048 points 0.218 / 0.205 / 0.286 ms, 5,000 0.413 / 0.395 / 0.490, 20,000 1.486 / 1.250 /
 # 1.310, 50,000 3.497 / 2.928 / 3.104.  20,000 is the smallest swept size at which a larger tile wins
@@ -116,8 +117,8 @@ class HiJetOp:
     def __init__(self, net, plan_hi, out_rows, X_all, n_hi, device, tile=None):
         """``tile``: points per workgroup - ``None`` picks by ``n_hi`` (the 4-point entry points below
         ``AUTO_TILE_N``, else the first of ``TILES`` that fits LDS, forward and adjoint chain each), ``4``
-        forces the 4-point entry points, ``8`` / ``16`` the tile kernels (ValueError if LDS cannot
-        hold it).  :attr:`tile` / :attr:`tile_bwd`: what the forward / the chain run with;
+        forces the 4-point entry points, ``8`` / ``16`` those tiles through the tile entry points
+        (ValueError if LDS cannot hold it).  :attr:`tile` / :attr:`tile_bwd`: what the forward / the chain run with;
         :attr:`entry`: ``"hi"`` (4-point entry points) or ``"hi_tile"``."""
         self.lib = _lib.load(required=True)
         self.net = net

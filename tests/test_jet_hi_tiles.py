@@ -1,14 +1,16 @@
-"""The 8- and 16-point tile variant of the high-order jet kernels (csrc/jet_hi.hip: jet_hi_fwd_tile_kernel,
-jet_hi_chain_tile_kernel, the tdq_jet_hi_tile_* entry points) against float64.
+"""The high-order jet kernels (csrc/jet_hi.hip: jet_hi_fwd_kernel, jet_hi_chain_kernel) at 8 and 16 points
+per workgroup, and every tile through the tdq_jet_hi_tile_* entry points, against float64.
 
 Same oracle as tests/test_jet_hi_oracle.py (its ``_measure``: forward per stream and gradient per
 parameter block against ``jet_forward`` in fp64 at the family's 1e-4, every stream owned and the
 production shape, NaN-filled buffers, bitwise determinism, part 1 + part 2 == part 0), with the tile
 forced through ``HiJetOp(tile=)``.  The production shape here also runs through the C entry points
-with ``j0 != 0``.  The cases are the edges of the tile kernels: a partial last workgroup for both
+with ``j0 != 0``.  The cases are the edges of the larger tiles: a partial last workgroup for both
 tiles, S = 8 with every GEMM row tile live, unaligned layer offsets, fewer points than one tile, one
 hidden layer, both sides of the three-term split, several weight-gradient splits with a partial
-staging batch and more than 256 vector-slab rows, and the 4-point kernels' rows for comparison.
+staging batch and more than 256 vector-slab rows, tile 4 through the tile entry points (alone and as
+the chain's half of a mixed pair: what the automatic choice gives where 8 points do not fit the
+chain), and the rows of tile 4 for comparison.
 """
 import ctypes
 import functools
@@ -38,6 +40,11 @@ CASES = [
     (8, [2] + [24] * 4 + [1], [(0, 0, 0, 0)], 21, 5, "chain"),     # two-term side of the depth threshold
     (16, [2, 128, 128, 128, 1], [(0, 0, 0, 0)], 4100, 5, "chain"),  # 17 splits, partial batch, 257 vslab rows
     (16, [2, 24, 24, 24, 24, 24, 1], [(0, 0, 0)], 37, 4, "chain"),  # LDS boundary: 16 points, three-term, S = 4
+    # tile 4 through the tile entry points (S-sized scratch, 256-point splits): the fallback of the
+    # automatic choice (three-term split, S = 8: all 32 GEMM rows live); HiJetOp(tile=4) means the small
+    # entry points, so only the direct-call shape reaches them (SHAPES below)
+    (4, [2] + [24] * 5 + [1], [(0, 0, 0, 1)], 21, 8, "table"),
+    ((8, 4), [2, 128, 128, 1], [(0, 0, 0), (1,)], 19, 5, "table"),  # mixed pair; partial last workgroup for both
 ]
 IDS = [f"t{c[0] if isinstance(c[0], int) else '+'.join(map(str, c[0]))}-" + "x".join(map(str, c[1][:2] + c[1][-1:])) + f"L{len(c[1]) - 2}-S{c[4]}-n{c[3]}" for c in CASES]
 
@@ -50,7 +57,8 @@ def force_tile(monkeypatch):
         monkeypatch.setattr(jet_hi, "HiJetOp", functools.partial(jet_hi.HiJetOp, tile=tile))
 
         def fwd(op, J, P, ldJ, j0):
-            assert op.entry == "hi_tile" and (op.tile, op.tile_bwd) == (tile if isinstance(tile, tuple) else (tile, tile))
+            pair = tile if isinstance(tile, tuple) else (tile, tile)
+            assert op.entry == ("hi" if pair == (4, 4) else "hi_tile") and (op.tile, op.tile_bwd) == pair
             rc = op.lib.tdq_jet_hi_tile_fwd(_lib.ptr(op.X), op.n_hi, _lib.ptr(P), *op._args(), _lib.ptr(J), ldJ, j0,
                                             _lib.ptr(op.Z), op.tile, _lib.stream_ptr(op.X.device))
             _lib.check(rc, "tdq_jet_hi_tile_fwd")
@@ -75,9 +83,13 @@ def _assert_bounds(tag, ferr, berr, gerr):
     assert gerr < BOUND, (tag, gerr)
 
 
+# the two HiJetOp shapes and the direct call of the C tile entry points; tile 4 alone only the latter
+SHAPES = [pytest.param(*c, shape, id=f"{i}-{shape}") for shape in ("all-owned", "production", "production-j0")
+          for c, i in zip(CASES, IDS) if c[0] != 4 or shape == "production-j0"]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", ["all-owned", "production", "production-j0"])
-@pytest.mark.parametrize("tile,sizes,reqs,n,S,variant", CASES, ids=IDS)
+@pytest.mark.parametrize("tile,sizes,reqs,n,S,variant,shape", SHAPES)
 def test_tile_kernels_match_fp64_jet(force_tile, tile, sizes, reqs, n, S, variant, shape):
     """Forward per owned stream and gradient per parameter block below 1e-4 of the fp64 torch jet with
     the tile forced: every stream owned; the production shape through HiJetOp (top orders owned,
@@ -93,8 +105,8 @@ def test_tile_kernels_match_fp64_jet(force_tile, tile, sizes, reqs, n, S, varian
 @pytest.mark.gpu
 @pytest.mark.parametrize("tile", [8, 16])
 def test_tile_forward_rows_are_the_four_point_kernels_rows(tile):
-    """[2,128,128,1], the KdV plan, 1024 points: per row the tile kernels run the 4-point kernels'
-    arithmetic (k order, the three products, hi_sigmas, the output layer's sum); the forward rows agree
+    """[2,128,128,1], the KdV plan, 1024 points: per row the kernels run the same arithmetic at every
+    tile (k order, the three products, hi_sigmas, the output layer's sum); the forward rows agree
     within 2e-6 of each stream's norm, a few fp32 ulps (printed, with whether they are bit-equal: the
     compiler may contract the elementwise code of two instantiations differently).  The gradient takes
     other split counts and slab rows, another summation order: printed, and checked against fp64 at
