@@ -90,6 +90,10 @@ def solver_state(solver, include_state=True):
                 v.append((vv if rep else _gather_rows(vv, ctx)).detach().cpu())
             st[key] = {"m": m, "v": v, "t": float(0 if opt._t is None else opt._t.item()),
                        "hyper": [opt.learning_rate, opt.beta_1, opt.beta_2, opt.epsilon]}
+        if getattr(solver, "isCausal", False):   # the weight array itself is saved with the lambdas
+            st["causal"] = {"eps_index": int(solver._causal_eps_index), "epoch": int(solver._causal_epoch),
+                            "done": bool(solver._causal_done),
+                            "history": [[int(e), float(eps), float(w)] for e, eps, w in solver.causal_history]}
         s = solver._state
         if s is not None:
             st["epoch"] = int(s["epoch_host"])
@@ -166,6 +170,14 @@ def load_into_solver(solver, path, restore_state=False):
                         m.copy_(sm.reshape(m.shape).to(m.device))
                         v.copy_(sv.reshape(v.shape).to(v.device))
                 opt.step_counter(solver.device).fill_(st[key]["t"])
+    if "causal" in st and getattr(solver, "isCausal", False):
+        cz = st["causal"]
+        if 0 <= int(cz["eps_index"]) < len(solver.causal_eps):
+            solver._causal_eps_index = int(cz["eps_index"])
+            solver._causal_epoch = int(cz["epoch"])
+            solver._causal_done = bool(cz["done"])
+            solver.causal_history = [(int(e), float(eps), float(w)) for e, eps, w in cz["history"]]
+            solver._causal_op().set_eps(solver._causal_eps_index)
     if "opt_theta" in st:
         m, v = solver.tf_optimizer.state_for(net.flat)
         m.copy_(st["opt_theta"]["m"][0].to(m.device))

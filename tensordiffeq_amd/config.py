@@ -44,6 +44,9 @@ nan_check              TDQ_NAN_CHECK=0 disables    device loss-history NaN/Inf s
 (hi_tile)              TDQ_HI_TILE                 auto | 4 | 8 | 16: points per workgroup of the
                                                    high-order kernels (auto: 8 from 20,000 points on)
 (lbfgs_fused)          TDQ_LBFGS_FUSED=0           five-launch L-BFGS update instead of two
+(causal_kernel)        TDQ_CAUSAL_KERNEL=0         causal weights (Adaptive_type 4) updated by the torch
+                                                   mirror on the GPU instead of csrc/causal.hip
+                                                   (ops/causal.py: the A/B and fallback switch)
 (profiling)            TDQ_PROFILE                 directory: every fit() runs under torch.profiler
                                                    -> trace.json + kernels.txt (profiling.py)
 =====================  ==========================  =========================================

@@ -7,7 +7,8 @@ weights that produced the loss - B8), one Keras-Adam update of theta and one Ada
 of the self-adaptive weights (fused HIP kernel on GPU), and a device-side loss-history write.
 Nothing in the step reads back to the host, so on a GPU the whole step is captured once into a
 HIP graph and replayed (reference: a ``tf.function`` step plus a host sync every epoch,
-fit.py:41-55).  Under DP the collective sits between two captured graphs.
+fit.py:41-55).  Under DP the collective sits between two captured graphs.  With causal training weights
+(``ops/causal.py``) the step ends with their update from its own loss pass, also inside the graph.
 
 :class:`LossGradEngine` - ``(f, grad theta)`` at a given flat parameter vector, the objective
 of both L-BFGS variants; also graph-captured on GPU.
@@ -77,9 +78,13 @@ class AdamEngine:
     earlier eager backward would otherwise make autograd sync the legacy null stream inside
     the HIP-graph capture."""
 
-    def __init__(self, solver, program, groups, n_steps_hint=0, lambdas=None, bind=None):
+    def __init__(self, solver, program, groups, n_steps_hint=0, lambdas=None, bind=None, causal=None):
         self.s = solver
         self.program = program
+        # ops.causal.CausalOp or None: after every step's loss pass it rewrites the per-point residual
+        # weights from that pass's adjoint of the weight array (c f^2), for the next step
+        self.causal = causal
+        self._r2 = None
         self.groups = [g for g in groups if g.tensors]
         self.flat = groups[0].tensors[0]
         self.lambdas = lambdas if lambdas is not None else []
@@ -196,12 +201,23 @@ class AdamEngine:
         optimizer step paths only): the fused loss leaves the total to the bookkeeping kernel."""
         fop = getattr(self.program, "fused_op", None)
         self._sum_terms = fop is not None and for_step
+        cz = self.causal
         if fop is not None:
-            return self._phase_a_fused(fop, for_step)
+            out = self._phase_a_fused(fop, for_step)
+            if cz is not None:
+                self._r2 = fop.dlam[cz.slot]
+            return out
         alias = [t.detach().requires_grad_(True) for t in self.wrt]
-        loss, vals = self.program.evaluate(**self.bind(alias))
+        kw = self.bind(alias)
+        if cz is not None:   # the same quantity by autograd with respect to the weight array
+            lam = self.lambdas[cz.lam_index].detach().requires_grad_(True)
+            kw["lambdas"] = [lam if i == cz.lam_index else l for i, l in enumerate(kw["lambdas"])]
+            alias = alias + [lam]
+        loss, vals = self.program.evaluate(**kw)
         grads = torch.autograd.grad(loss, alias, allow_unused=True)
         grads = [torch.zeros_like(w) if g is None else g for g, w in zip(grads, alias)]
+        if cz is not None:
+            self._r2 = grads.pop().contiguous()
         terms = [vals[n].detach().reshape(()) for n in self.term_names]
         return loss.detach(), grads, terms
 
@@ -254,6 +270,8 @@ class AdamEngine:
         # theta descent + SA-weight ascent in one launch; it also snapshots the best weights
         snap = (st["best_flat"], st["improved"]) if self.groups[0].tensors[0] is self.flat else None
         fused.adam_multi_opts(opt_groups, snapshot=snap)
+        if self.causal is not None:
+            self.causal.update(self._r2)
         return loss
 
     # ------------------------------------------------------------ fused step tail ------
@@ -299,6 +317,8 @@ class AdamEngine:
         jet_hip.step_tail(saved, work, grad, fop, st, self.counters, packed[0], packed[1], st["best_flat"],
                           write_images=in_graph, c_first=pre, gextra=hi.grad if hi is not None else None,
                           best_prev=self._best_prev if one else None, **kw)
+        if self.causal is not None:
+            self.causal.update(fop.dlam[self.causal.slot])
         self._tail_saved = saved
         self.tail_launches = 1 if one else 2
         return fop.total

@@ -499,7 +499,9 @@ def _build(prog, lambdas):
                 scal_id[("lam", t.lam)] = len(fl.scal_slots)
                 fl.scal_slots.append(("lam", t.lam))
             return Sym(g, g.add(("scal", ("lam", t.lam))))
-        if prog.weight_outside_sum:
+        # (the causal mode's residual is g_MSE, element-wise g(lambda) f^2, beside outside-sum scalars)
+        if prog.weight_outside_sum and not (t.kind == "residual" and prog.g is not None
+                                            and getattr(prog, "causal", False)):
             raise TraceError("outside-sum weighting with per-point weights")
         if t.lam not in lam_id:
             lam_id[t.lam] = len(fl.lam_slots)

@@ -8,7 +8,8 @@ newton_eager)``, ``get_loss_and_flat_grad``, ``predict(X_star, best_model=False)
 ``lambdas``, ``lambdas_map``, ``losses``, ``min_loss``, ``best_epoch``, ``best_model``.
 
 Implements the reference's *intent* where it is broken: ``Adaptive_type`` accepts
-ints and names, type 3 / ``"ntk"`` being the NTK weighting of ``ops/ntk.py`` (B14); SA works with minibatches and under DP (B5); DP shards points (B3) and
+ints and names, type 3 / ``"ntk"`` being the NTK weighting of ``ops/ntk.py`` (B14) and type 4 / ``"causal"``
+the causal training weights of ``ops/causal.py`` (not in the reference); SA works with minibatches and under DP (B5); DP shards points (B3) and
 reports the true global loss (B4); repeated ``fit`` calls resume (B6); L-BFGS runs under DP
 (B7); best weights are real snapshots (B8); the data-assimilation term is used (B17).
 """
@@ -33,17 +34,26 @@ from .networks import FlatModule, TanhMLP
 _ADAPTIVE = {0: 0, "none": 0, "baseline": 0, "pinn": 0,
              1: 1, "self-adaptive": 1, "self_adaptive": 1, "sa": 1, "sa-pinn": 1,
              2: 2, "loss-weights": 2, "self-adaptive-loss": 2, "weight_outside_sum": 2,
-             3: 3, "ntk": 3}
+             3: 3, "ntk": 3,
+             4: 4, "causal": 4}
 
 
-def parse_adaptive_type(a, ntk=False):
-    """``ntk=True``: the caller implements NTK weighting (``CollocationSolverND.compile``)."""
+def _identity(lam):
+    """``g`` of the causal mode: the residual term is ``mean(lambda_i f_i^2)``."""
+    return lam
+
+
+def parse_adaptive_type(a, ntk=False, causal=False):
+    """``ntk=True`` / ``causal=True``: the caller implements NTK / causal weighting
+    (``CollocationSolverND.compile``)."""
     key = a.lower() if isinstance(a, str) else a
     if key not in _ADAPTIVE:
         raise Exception("Adaptive method invalid!")
     v = _ADAPTIVE[key]
     if v == 3 and not ntk:
         raise NotImplementedError("NTK adaptive weighting (Adaptive_type=3) is not implemented")
+    if v == 4 and not causal:
+        raise NotImplementedError("causal training weights (Adaptive_type=4) are not implemented")
     return v
 
 
@@ -76,6 +86,8 @@ class CollocationSolverND:
         self.isNTK = False
         self.ntk_every = 100
         self.ntk_history = []   # (epoch, {term: T_k}, {term: lambda_k}) per NTK update
+        self.isCausal = False
+        self.causal_history = []   # (epoch, eps in force after the check, min_b W_b) per eps check
         self.data_x = self.data_t = self.data_s = None
         self._engine = None
         self._lbfgs_engine = None
@@ -90,7 +102,9 @@ class CollocationSolverND:
     def compile(self, layer_sizes, f_model, domain, bcs, Adaptive_type=0, dict_adaptive=None,
                 init_weights=None, g=None, dist=False, backend="auto", device=None,
                 periodic_legacy=False, seed=None, network=None, precision=None, metrics_path=None,
-                log_every=None, newton_precision=None, lbfgs_stop=None, newton_schedule=None, ntk_every=100):
+                log_every=None, newton_precision=None, lbfgs_stop=None, newton_schedule=None, ntk_every=100,
+                causal_eps=1.0, causal_bins=32, causal_delta=0.99, causal_every=100, causal_stop=False,
+                causal_bc_weights=None):
         from ..config import SolverConfig
         self.config = SolverConfig.from_env(backend=None if backend == "auto" else backend, precision=precision,
                                             seed=seed, metrics_path=metrics_path, log_every=log_every,
@@ -155,11 +169,18 @@ class CollocationSolverND:
         if ctx.is_distributed:
             ctx.broadcast_(self.u_model.flat.data)
 
-        self.Adaptive_type = parse_adaptive_type(Adaptive_type, ntk=True)
+        self.Adaptive_type = parse_adaptive_type(Adaptive_type, ntk=True, causal=True)
         self.isAdaptive = self.Adaptive_type in (1, 2)
         self.isNTK = self.Adaptive_type == 3
-        # NTK weights multiply the terms like type 2's: lambda_k * mean(f^2)
-        self.weight_outside_sum = self.Adaptive_type in (2, 3)
+        self.isCausal = self.Adaptive_type == 4
+        # NTK weights multiply the terms like type 2's: lambda_k * mean(f^2); so do the causal mode's
+        # fixed BC / IC / data scalars, beside its per-point residual weights (g_MSE, g the identity)
+        self.weight_outside_sum = self.Adaptive_type in (2, 3, 4)
+        if self.isCausal:
+            self._check_causal(dict_adaptive, init_weights, g, backend, causal_eps, causal_bins, causal_delta,
+                               causal_every, causal_bc_weights)
+            self.causal_stop = bool(causal_stop)
+            self.g = _identity
         if self.isNTK:
             if dict_adaptive is not None or init_weights is not None:
                 raise Exception("NTK weights are computed from the network, one per loss term, but weight vectors "
@@ -196,6 +217,8 @@ class CollocationSolverND:
         if self.isNTK:
             self._init_ntk_lambdas()
             self._ntk_op()   # a loss the tracer cannot fuse is refused here
+        if self.isCausal:
+            self._init_causal_lambdas()
         for i, bc in enumerate(self.bcs):   # a target that does not fit the outputs is refused here
             if bc.isInit or bc.isDirichlect:
                 self._value_target(f"BC_{i} ({type(bc).__name__})", bc.val, getattr(bc, "outputs", None))
@@ -268,6 +291,124 @@ class CollocationSolverND:
                             "bcs": [i for i, k in enumerate(keys) if k[0] == "bc"]}
         if self.assimilate:
             self.lambdas_map["data"] = [len(keys) - 1]
+
+    # ---------------------------------------------------------------- causal weights ----
+    def _check_causal(self, dict_adaptive, init_weights, g, backend, eps, bins, delta, every, bc_weights):
+        """The causal mode's refusals, each naming its reason, and its settings."""
+        tv = getattr(self.domain, "time_var", None)
+        if tv is None or tv not in self.domain.vars:
+            raise ValueError("causal training weights bin the collocation points by time, but the domain has no "
+                             "time_var")
+        if dict_adaptive is not None or init_weights is not None:
+            raise Exception("causal weights are computed from the residuals, one per collocation point, but weight "
+                            "vectors were provided. Set the weight vectors to \"none\" to continue")
+        if g is not None:
+            raise Exception("causal weights multiply the squared residuals directly; a weight function g was "
+                            "provided. Set g to \"none\" to continue")
+        if backend == "autograd":
+            raise ValueError("causal training weights need the jet path (backend 'jet' or 'hip'), backend "
+                             "'autograd' was requested")
+        if self.dist:
+            raise ValueError("causal training weights are not available with dist=True: the bins' residual "
+                             "means would need an all-reduce in every step")
+        if isinstance(bins, bool) or int(bins) != bins or not 1 <= int(bins) <= 1024:
+            raise ValueError(f"causal_bins must be an integer in 1..1024, got {bins}")
+        eps_list = [float(e) for e in (eps if isinstance(eps, (list, tuple)) else [eps])]
+        if not eps_list or any(not (math.isfinite(e) and e >= 0.0) for e in eps_list) \
+                or any(b <= a for a, b in zip(eps_list, eps_list[1:])):
+            raise ValueError(f"causal_eps must be a non-negative float or an increasing list of them, got {eps}")
+        if int(every) < 1:
+            raise ValueError(f"causal_every must be positive, got {every}")
+        n_res = self._residual_count()
+        if n_res != 1:
+            raise ValueError(f"causal training weights take one residual output, f_model returns {n_res}")
+        self._n_res = n_res
+        n_terms = len(self.bcs) + (1 if self.assimilate else 0)
+        bcw = [1.0] * n_terms if bc_weights is None else [float(w) for w in bc_weights]
+        if len(bcw) != n_terms:
+            raise ValueError(f"causal_bc_weights: {len(bcw)} weights for {n_terms} BC / IC / data terms")
+        self.causal_eps = eps_list
+        self.causal_bins, self.causal_delta, self.causal_every = int(bins), float(delta), int(every)
+        self.causal_bc_weights = bcw
+        self.causal_history = []
+        self._causal_epoch = 0
+        self._causal_eps_index = 0
+        self._causal_done = False
+        self._causal_ops = {}
+
+    def _init_causal_lambdas(self):
+        """The per-point residual weights ``(N_f, 1)``, ones, then one fixed scalar per BC / IC / data
+        term (the untrained-scalar slots of :meth:`_init_ntk_lambdas`).  No optimizer owns them; the
+        residual weights are overwritten in place after every loss pass (ops/causal.py)."""
+        keys = [("residual", 0)] + [("bc", i) for i in range(len(self.bcs))]
+        if self.assimilate:
+            keys.append(("data", 0))
+        self.lambdas = [torch.ones((self.X_f_local.shape[0], 1), dtype=torch.float32, device=self.device)]
+        self.lambdas += [torch.full((), w, dtype=torch.float32, device=self.device) for w in self.causal_bc_weights]
+        self._lam_for = {k: i for i, k in enumerate(keys)}
+        self._lam_kind = ["residual" if k[0] == "residual" else "bc" for k in keys]
+        self.lambdas_map = {"residual": [0], "bcs": [i for i, k in enumerate(keys) if k[0] == "bc"]}
+        if self.assimilate:
+            self.lambdas_map["data"] = [len(keys) - 1]
+
+    def _causal_op(self, prog=None):
+        """The weight update of the full-batch program (``ops/causal.py``), rebuilt with the program."""
+        from ..ops import causal
+        prog = self.program() if prog is None else prog
+        op = self._causal_ops.get("op")
+        if op is None or op.prog is not prog:
+            tv = self.domain.time_var
+            j = self.domain.vars.index(tv)
+            t0, t1 = (float(v) for v in self.domain.get_dict(tv)["range"])
+            term = next(t for t in prog.terms if t.kind == "residual")
+            n = prog.segments[term.seg].n
+            c = term.scale / (term.denom if term.denom is not None else n)
+            op = causal.CausalOp(prog, prog.fused_op, self.X_f_local[:, j], (t0, t1), self.causal_bins,
+                                 self.causal_eps, self.device, self.lambdas[0], 0, 1.0 / c)
+            op.set_eps(self._causal_eps_index)
+            self._causal_ops = {"op": op}
+            self._programs.pop(("engine", None), None)   # its captured step calls the old update
+        return op
+
+    def causal_weights(self):
+        """The ``M`` bin weights ``W_b`` of the last update (a CPU tensor)."""
+        if not self.isCausal:
+            raise ValueError("causal_weights() needs Adaptive_type='causal'")
+        return self._causal_op().w_bins.detach().cpu().clone()
+
+    def _causal_prime(self):
+        """One loss evaluation at the current parameters, then the weight update: the weights of the
+        first step of a ``fit`` call.  Runs eagerly, before any capture."""
+        op = self._causal_op()
+        prog = op.prog
+        flat = self._flat()
+        fop = prog.fused_op
+        if fop is not None:
+            from ..ops import jet_hip
+            J, _ = jet_hip.forward_raw(prog.X_all, flat, prog.net, prog.plan, prog.precision, rows=fop.fl.n_streams)
+            if prog.hi_op is not None:
+                prog.hi_op.forward(J, flat)
+            fop(J)
+            op.update(fop.dlam[op.slot])
+            return
+        lam = self.lambdas[0].detach().requires_grad_(True)
+        loss, _ = prog.evaluate(flat.detach(), [lam] + [l.detach() for l in self.lambdas[1:]])
+        op.update(torch.autograd.grad(loss, lam)[0].contiguous())
+
+    def _causal_check(self, epoch):
+        """The eps schedule: with ``min_b W_b`` above ``causal_delta`` the next eps is written in
+        place (captured steps read it through its pointer).  Returns True when ``causal_stop`` ends
+        the Adam phase: the last eps has passed ``delta``."""
+        op = self._causal_op()
+        w = op.min_weight()
+        if w > self.causal_delta:
+            if op.eps_index + 1 < len(self.causal_eps):
+                op.set_eps(op.eps_index + 1)
+                self._causal_eps_index = op.eps_index
+            else:
+                self._causal_done = True
+        self.causal_history.append((int(epoch), float(self.causal_eps[op.eps_index]), w))
+        return self.causal_stop and self._causal_done
 
     def _ntk_op(self):
         """The trace evaluator of the full-batch program (``ops/ntk.py``), rebuilt with the program."""
@@ -359,6 +500,7 @@ class CollocationSolverND:
                            precision=precision or self.precision,
                            world=world, weight_outside_sum=self.weight_outside_sum, g=self.g,
                            periodic_legacy=self.periodic_legacy)
+        prog.causal = self.isCausal   # per-point residual weights beside outside-sum scalars (fusion.py)
         for i, bc in enumerate(self.bcs):
             lam = self._lam_for.get(("bc", i))
             name = f"BC_{i}"
@@ -470,8 +612,8 @@ class CollocationSolverND:
 
     @property
     def variables(self):
-        # (NTK weights are not trained: no gradient is taken with respect to them)
-        return [self._flat()] + ([] if self.isNTK else list(self.lambdas or []))
+        # (NTK and causal weights are not trained: no gradient is taken with respect to them)
+        return [self._flat()] + ([] if self.isNTK or self.isCausal else list(self.lambdas or []))
 
     def _outside_sum_weights(self):
         """Per-point residual weights enter through MSE's outside sum (Adaptive_type 2 without
@@ -522,12 +664,13 @@ class CollocationSolverND:
         if eng is None:
             groups = [ParamGroup([self._flat()], lambda: self.tf_optimizer, 1.0)]
             bind = None
-            if self.isNTK:   # the weights enter the loss but no optimizer owns them
+            if self.isNTK or self.isCausal:   # the weights enter the loss but no optimizer owns them
                 bind = lambda alias: {"params": alias[0], "lambdas": self.lambdas}  # noqa: E731
             else:
                 groups.append(ParamGroup(self.lambdas, lambda: self.tf_optimizer_weights, -1.0,
                                          self._lam_replicated()))
-            eng = AdamEngine(self, prog, groups, n_steps_hint=n_hint, lambdas=self.lambdas, bind=bind)
+            eng = AdamEngine(self, prog, groups, n_steps_hint=n_hint, lambdas=self.lambdas, bind=bind,
+                             causal=self._causal_op(prog) if self.isCausal else None)
             self._programs[key] = eng
         return eng
 
@@ -558,6 +701,9 @@ class CollocationSolverND:
 
     def _fit(self, tf_iter, newton_iter, batch_sz, newton_eager):
         ctx = self.dist_ctx
+        if self.isCausal and batch_sz is not None:
+            raise ValueError("causal training weights need full-batch steps (the bins' residual means cover every "
+                             "collocation point): batch_sz must be None")
         batches = self.minibatches(batch_sz)
         if self.verbose and ctx.rank == 0:
             print_screen(self)
@@ -595,6 +741,19 @@ class CollocationSolverND:
                     eng.run(n, progress=lambda k, loss, base=done: progress(base + k, loss), log_every=self.log_every)
                     done += n
                     self._ntk_epoch += n
+            elif batches == [None] and self.isCausal:
+                # segments between eps checks: eps and the weights change in place, the captured step stays
+                self._causal_prime()
+                eng = self._get_engine(None, tf_iter)
+                done = 0
+                while done < tf_iter:
+                    if self._causal_epoch % self.causal_every == 0 and self._causal_check(self._causal_epoch):
+                        break
+                    n = min(tf_iter - done, self.causal_every - self._causal_epoch % self.causal_every)
+                    eng.run(n, progress=lambda k, loss, base=done: progress(base + k, loss), log_every=self.log_every)
+                    done += n
+                    self._causal_epoch += n
+                tf_iter = done
             elif batches == [None]:
                 eng = self._get_engine(None, tf_iter)
                 eng.run(tf_iter, progress=progress, log_every=self.log_every)

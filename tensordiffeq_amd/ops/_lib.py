@@ -19,7 +19,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TDQ_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "csrc", "libtdq_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _lock = threading.Lock()
 _lib = None
@@ -91,6 +91,9 @@ def _declare(lib):
         # one layer's Gram share of the norms from fp32 planes (csrc/ntk_gram.hip, the layer-wise NTK path)
         "tdq_ntk_gram": (I, [P, L, I, P, L, I, I, I, I, I, I, I, P, P]),
         "tdq_loss_seed": (I, [P, P, P, P, P, I, I, I, I, I, P, P, P] + [I] * 10 + [P]),
+        # causal training weights (csrc/causal.hip, ops/causal.py)
+        "tdq_causal_work_doubles": (I, [I]),
+        "tdq_causal_update": (I, [P, D, P, P, P, I, I, P, P, P, P, P, P]),
         "tdq_lbfgs_nst": (I, []),
         "tdq_lbfgs_ticket_ints": (I, []),
         "tdq_lbfgs_update": (I, [P] * 14 + [I] * 6 + [D] * 4 + [I, P]),

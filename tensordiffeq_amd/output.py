@@ -33,3 +33,6 @@ def print_screen(model, discovery_model=False):
         print(f"\nbackend: {prog.backend}" + (f"  streams: {prog.plan.streams}" if prog.plan else ""))
     if getattr(model, "isNTK", False):
         print(f"adaptive weights: NTK (one weight per loss term, recomputed every {model.ntk_every} Adam steps)")
+    if getattr(model, "isCausal", False):
+        print(f"adaptive weights: causal ({model.causal_bins} time bins, eps schedule {model.causal_eps}, "
+              f"checked every {model.causal_every} Adam steps)")
