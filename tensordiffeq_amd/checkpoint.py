@@ -94,6 +94,9 @@ def solver_state(solver, include_state=True):
             st["causal"] = {"eps_index": int(solver._causal_eps_index), "epoch": int(solver._causal_epoch),
                             "done": bool(solver._causal_done),
                             "history": [[int(e), float(eps), float(w)] for e, eps, w in solver.causal_history]}
+        if getattr(solver, "isR3", False):   # the population the resampling has reached, its seed and counter
+            st["r3"] = {"points": solver.collocation_points(), "seed": int(solver.resample_seed),
+                        "step": int(solver._r3_state)}
         s = solver._state
         if s is not None:
             st["epoch"] = int(s["epoch_host"])
@@ -178,6 +181,8 @@ def load_into_solver(solver, path, restore_state=False):
             solver._causal_done = bool(cz["done"])
             solver.causal_history = [(int(e), float(eps), float(w)) for e, eps, w in cz["history"]]
             solver._causal_op().set_eps(solver._causal_eps_index)
+    if "r3" in st and getattr(solver, "isR3", False):
+        solver._r3_restore(st["r3"]["points"], st["r3"]["seed"], st["r3"]["step"])
     if "opt_theta" in st:
         m, v = solver.tf_optimizer.state_for(net.flat)
         m.copy_(st["opt_theta"]["m"][0].to(m.device))

@@ -47,6 +47,9 @@ nan_check              TDQ_NAN_CHECK=0 disables    device loss-history NaN/Inf s
 (causal_kernel)        TDQ_CAUSAL_KERNEL=0         causal weights (Adaptive_type 4) updated by the torch
                                                    mirror on the GPU instead of csrc/causal.hip
                                                    (ops/causal.py: the A/B and fallback switch)
+(r3_kernel)            TDQ_R3_KERNEL=0             R3 resampling (compile(resample="r3")) by the torch
+                                                   mirror on the GPU instead of csrc/r3.hip
+                                                   (ops/r3.py: the A/B and fallback switch)
 (profiling)            TDQ_PROFILE                 directory: every fit() runs under torch.profiler
                                                    -> trace.json + kernels.txt (profiling.py)
 =====================  ==========================  =========================================

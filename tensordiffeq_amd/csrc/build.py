@@ -46,7 +46,9 @@ def _flags(defines=()):
 # (-ffp-contract=fast) also lets the backend fuse inside the expansions of logf / sinf / cosf / expf /
 # tanhf / powf (logf: the final v_mul + v_add of the ln(2) scaling becomes one v_fmac), a last-bit
 # difference between the two (tests/test_loss_jit.py, program "log").
-FILE_FLAGS = {"loss_fused.hip": ["-ffp-contract=on"]}
+# r3.hip: the resampled coordinate lo + u * (hi - lo) is specified with the multiply and the add rounded
+# separately (ops/r3.py's torch mirror gives the same bits), so nothing in that file may be contracted.
+FILE_FLAGS = {"loss_fused.hip": ["-ffp-contract=on"], "r3.hip": ["-ffp-contract=off"]}
 
 
 def source_files():

@@ -8,7 +8,8 @@ of the self-adaptive weights (fused HIP kernel on GPU), and a device-side loss-h
 Nothing in the step reads back to the host, so on a GPU the whole step is captured once into a
 HIP graph and replayed (reference: a ``tf.function`` step plus a host sync every epoch,
 fit.py:41-55).  Under DP the collective sits between two captured graphs.  With causal training weights
-(``ops/causal.py``) the step ends with their update from its own loss pass, also inside the graph.
+(``ops/causal.py``) the step ends with their update from its own loss pass, also inside the graph; with R3
+resampling (``ops/r3.py``) it ends, in the same way, with the move of the collocation points.
 
 :class:`LossGradEngine` - ``(f, grad theta)`` at a given flat parameter vector, the objective
 of both L-BFGS variants; also graph-captured on GPU.
@@ -78,12 +79,18 @@ class AdamEngine:
     earlier eager backward would otherwise make autograd sync the legacy null stream inside
     the HIP-graph capture."""
 
-    def __init__(self, solver, program, groups, n_steps_hint=0, lambdas=None, bind=None, causal=None):
+    def __init__(self, solver, program, groups, n_steps_hint=0, lambdas=None, bind=None, causal=None,
+                 resample=None):
         self.s = solver
         self.program = program
         # ops.causal.CausalOp or None: after every step's loss pass it rewrites the per-point residual
-        # weights from that pass's adjoint of the weight array (c f^2), for the next step
-        self.causal = causal
+        # weights from that pass's adjoint of the weight array (c f^2), for the next step.
+        # ops.r3.R3Op or None: at the same places, from the same adjoint (of an array of ones), it moves
+        # the residual points for the next step.  Both have ``slot``, ``lam_index`` and ``update(r2)``;
+        # a solver has at most one of them
+        if causal is not None and resample is not None:
+            raise ValueError("AdamEngine: causal weights and resampling together")
+        self.after_loss = causal if causal is not None else resample
         self._r2 = None
         self.groups = [g for g in groups if g.tensors]
         self.flat = groups[0].tensors[0]
@@ -201,7 +208,7 @@ class AdamEngine:
         optimizer step paths only): the fused loss leaves the total to the bookkeeping kernel."""
         fop = getattr(self.program, "fused_op", None)
         self._sum_terms = fop is not None and for_step
-        cz = self.causal
+        cz = self.after_loss
         if fop is not None:
             out = self._phase_a_fused(fop, for_step)
             if cz is not None:
@@ -270,8 +277,8 @@ class AdamEngine:
         # theta descent + SA-weight ascent in one launch; it also snapshots the best weights
         snap = (st["best_flat"], st["improved"]) if self.groups[0].tensors[0] is self.flat else None
         fused.adam_multi_opts(opt_groups, snapshot=snap)
-        if self.causal is not None:
-            self.causal.update(self._r2)
+        if self.after_loss is not None:
+            self.after_loss.update(self._r2)
         return loss
 
     # ------------------------------------------------------------ fused step tail ------
@@ -317,8 +324,8 @@ class AdamEngine:
         jet_hip.step_tail(saved, work, grad, fop, st, self.counters, packed[0], packed[1], st["best_flat"],
                           write_images=in_graph, c_first=pre, gextra=hi.grad if hi is not None else None,
                           best_prev=self._best_prev if one else None, **kw)
-        if self.causal is not None:
-            self.causal.update(fop.dlam[self.causal.slot])
+        if self.after_loss is not None:
+            self.after_loss.update(fop.dlam[self.after_loss.slot])
         self._tail_saved = saved
         self.tail_launches = 1 if one else 2
         return fop.total

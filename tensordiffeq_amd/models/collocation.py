@@ -11,7 +11,9 @@ Implements the reference's *intent* where it is broken: ``Adap
 ints and names, type 3 / ``"ntk"`` being the NTK weighting of ``ops/ntk.py`` (B14) and type 4 / ``"causal"``
 the causal training weights of ``ops/causal.py`` (not in the reference); SA works with minibatches and under DP (B5); DP shards points (B3) and
 reports the true global loss (B4); repeated ``fit`` calls resume (B6); L-BFGS runs under DP
-(B7); best weights are real snapshots (B8); the data-assimilation term is used (B17).
+(B7); best weights are real snapshots (B8); the data-assimilation term is used (B17).  Beyond the reference,
+``compile(resample="r3")`` moves the collocation points after every Adam step (R3 resampling, ``ops/r3.py``;
+``collocation_points()``, ``resample_stats()``).
 """
 from __future__ import annotations
 
@@ -88,6 +90,7 @@ class CollocationSolverND:
         self.ntk_history = []   # (epoch, {term: T_k}, {term: lambda_k}) per NTK update
         self.isCausal = False
         self.causal_history = []   # (epoch, eps in force after the check, min_b W_b) per eps check
+        self.isR3 = False          # compile(resample="r3"): the collocation points move (ops/r3.py)
         self.data_x = self.data_t = self.data_s = None
         self._engine = None
         self._lbfgs_engine = None
@@ -104,7 +107,7 @@ class CollocationSolverND:
                 periodic_legacy=False, seed=None, network=None, precision=None, metrics_path=None,
                 log_every=None, newton_precision=None, lbfgs_stop=None, newton_schedule=None, ntk_every=100,
                 causal_eps=1.0, causal_bins=32, causal_delta=0.99, causal_every=100, causal_stop=False,
-                causal_bc_weights=None):
+                causal_bc_weights=None, resample=None, resample_seed=None):
         from ..config import SolverConfig
         self.config = SolverConfig.from_env(backend=None if backend == "auto" else backend, precision=precision,
                                             seed=seed, metrics_path=metrics_path, log_every=log_every,
@@ -181,6 +184,9 @@ class CollocationSolverND:
                                causal_every, causal_bc_weights)
             self.causal_stop = bool(causal_stop)
             self.g = _identity
+        self.isR3 = self._check_resample(resample, resample_seed, dict_adaptive, init_weights, g, backend)
+        if self.isR3:
+            self.g = _identity
         if self.isNTK:
             if dict_adaptive is not None or init_weights is not None:
                 raise Exception("NTK weights are computed from the network, one per loss term, but weight vectors "
@@ -219,6 +225,9 @@ class CollocationSolverND:
             self._ntk_op()   # a loss the tracer cannot fuse is refused here
         if self.isCausal:
             self._init_causal_lambdas()
+        if self.isR3:
+            self._init_r3_lambdas()
+            self._r3_residual_segment(self.program())   # a residual the mode cannot move is refused here
         for i, bc in enumerate(self.bcs):   # a target that does not fit the outputs is refused here
             if bc.isInit or bc.isDirichlect:
                 self._value_target(f"BC_{i} ({type(bc).__name__})", bc.val, getattr(bc, "outputs", None))
@@ -409,6 +418,146 @@ class CollocationSolverND:
                 self._causal_done = True
         self.causal_history.append((int(epoch), float(self.causal_eps[op.eps_index]), w))
         return self.causal_stop and self._causal_done
+
+    # ---------------------------------------------------------------- R3 resampling ----
+    def _check_resample(self, resample, seed, dict_adaptive, init_weights, g, backend):
+        """``compile(resample=...)``: whether the R3 mode is on, after its refusals, each naming its
+        reason."""
+        if resample is None:
+            return False
+        if not isinstance(resample, str) or resample.lower() != "r3":
+            raise ValueError(f"resample must be None or 'r3' (retain-resample-release), got {resample!r}")
+        if self.Adaptive_type != 0:
+            raise ValueError(f"R3 resampling moves the collocation points, but Adaptive_type={self.Adaptive_type} "
+                             "keeps weights that belong to fixed points (or to their time bins): Adaptive_type "
+                             "must be 0")
+        if dict_adaptive is not None or init_weights is not None:
+            raise Exception("R3 resampling keeps its own per-point array of ones, but weight vectors were "
+                            "provided. Set the weight vectors to \"none\" to continue")
+        if g is not None:
+            raise Exception("R3 resampling reads the squared residuals through a weight array of ones; a weight "
+                            "function g was provided. Set g to \"none\" to continue")
+        if backend == "autograd":
+            raise ValueError("R3 resampling needs the jet path (backend 'jet' or 'hip'), backend 'autograd' "
+                             "was requested")
+        if self.dist:
+            raise ValueError("R3 resampling is not available with dist=True: the mean of |f| over the population "
+                             "would need an all-reduce in every step")
+        box = []
+        for v in self.domain.vars:
+            rng = next((d["range"] for d in self.domain.domaindict if d["identifier"] == v), None)
+            if rng is None or not all(math.isfinite(float(b)) for b in rng) or not float(rng[1]) >= float(rng[0]):
+                raise ValueError(f"R3 resampling draws uniformly from the domain box, but variable {v!r} has no "
+                                 f"finite range ({rng})")
+            box.append((float(rng[0]), float(rng[1])))
+        if not 1 <= len(box) <= 8:
+            raise ValueError(f"R3 resampling takes 1..8 input variables, the domain has {len(box)}")
+        n_res = self._residual_count()
+        if n_res != 1:
+            raise ValueError(f"R3 resampling takes one residual output, f_model returns {n_res}")
+        self._n_res = n_res
+        if seed is None:
+            seed = self.config.seed if self.config.seed is not None else 0
+        self.resample = "r3"
+        self.resample_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._r3_box = box
+        self._r3_state = torch.zeros((), dtype=torch.int64, device=self.device)   # the step counter
+        self._r3_ops = {}
+        return True
+
+    def _init_r3_lambdas(self):
+        """The per-point array ``(N_f, 1)`` of ones on the residual term, ``g`` the identity: the loss is the
+        unweighted one, and the array's adjoint is ``c f^2``, what ops/r3.py reads.  No optimizer owns it
+        and nothing writes it."""
+        self.lambdas = [torch.ones((self.X_f_local.shape[0], 1), dtype=torch.float32, device=self.device)]
+        self._lam_for = {("residual", 0): 0}
+        self._lam_kind = ["residual"]
+        self.lambdas_map = {"residual": [0], "bcs": []}
+
+    def _r3_residual_segment(self, prog):
+        """Index of the residual segment of ``prog``, after the refusals that need the program."""
+        term = next(t for t in prog.terms if t.kind == "residual")
+        if prog.backend == "autograd":
+            raise ValueError("R3 resampling needs the jet path, but the loss callables run on the nested-autograd "
+                             "backend: " + "; ".join(prog.reasons or ["not jet-expressible"]))
+        if prog.segments[term.seg].hi:
+            raise ValueError("R3 resampling cannot move a residual of order 3 or 4: its points also live in the "
+                             "high-order kernels' own point set and scratch layout")
+        return term.seg
+
+    def _r3_op(self, prog=None):
+        """The resampling update of the full-batch program (``ops/r3.py``), rebuilt with the program: it
+        writes the residual rows of ``prog.X_all`` and, where the program has a one-launch step, of
+        ``FusedStepOp.X``.  The step counter is the solver's and survives a rebuild."""
+        from ..ops import r3
+        prog = self.program() if prog is None else prog
+        op = self._r3_ops.get("op")
+        if op is None or op.prog is not prog:
+            si = self._r3_residual_segment(prog)
+            prog.refresh_points(si)   # the segment's own X becomes a view of its X_all rows
+            seg = prog.segments[si]
+            term = next(t for t in prog.terms if t.kind == "residual")
+            c = term.scale / (term.denom if term.denom is not None else seg.n)
+            dests = [(prog.X_all, seg.offset)]
+            if self.device.type == "cuda" and prog.fused_op is not None:
+                from ..ops import fused_step
+                fs = fused_step.for_program(prog)
+                if fs is not None:
+                    start = fs.segment_start(si)
+                    if start is None:
+                        raise ValueError("R3 resampling: the residual points are not consecutive rows of the "
+                                         "one-launch step's point set")
+                    dests.append((fs.X, start))
+            op = r3.R3Op(prog, prog.fused_op, seg.n, self._r3_box, self.resample_seed, self._r3_state, dests,
+                         self.device, 0, 1.0 / c)
+            self._r3_ops = {"op": op}
+            self._programs.pop(("engine", None), None)   # its captured step calls the old update
+        return op
+
+    def _r3_sync(self, points=None):
+        """Every copy of the residual points outside the running program takes the current population
+        (``points``: a population to install everywhere, a checkpoint's): ``X_f_local`` (and so
+        ``X_f_in``), and every other built program - the bf16x3 objective of the L-BFGS phase may have been
+        built during Adam - through :meth:`LossProgram.refresh_points`, in place."""
+        op = self._r3_ops.get("op")
+        with torch.no_grad():
+            if points is not None:
+                self.X_f_local.copy_(points.to(self.X_f_local.device).reshape(self.X_f_local.shape))
+            elif op is not None:
+                self.X_f_local.copy_(op.points())
+        for key, prog in list(self._programs.items()):
+            if isinstance(prog, LossProgram) and key[:2] == ("batch", None):
+                if points is None and op is not None and prog is op.prog:
+                    continue
+                prog.refresh_points(self._r3_residual_segment(prog), self.X_f_local)
+
+    def _r3_restore(self, points, seed, step):
+        """A checkpoint's population, seed and counter (``resume``): the run continues its trajectory."""
+        if tuple(points.shape) != tuple(self.X_f_local.shape):
+            raise ValueError(f"checkpoint holds {tuple(points.shape)} collocation points, the solver "
+                             f"{tuple(self.X_f_local.shape)}")
+        self.resample_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._r3_state.fill_(int(step))
+        self._r3_ops = {}                             # the op carries the seed: rebuilt with the engine
+        self._programs.pop(("engine", None), None)
+        self._r3_sync(points.to(torch.float32))
+
+    def collocation_points(self):
+        """The current collocation points ``(N_f, d_in)`` (a CPU tensor): the population R3 resampling has
+        reached, or the fixed set."""
+        op = self._r3_ops.get("op") if self.isR3 else None
+        X = op.points() if op is not None else self.X_f_local
+        return X.detach().cpu().clone()
+
+    def resample_stats(self):
+        """``{"step", "released", "threshold"}``: the number of R3 updates so far, and the released rows
+        and the threshold ``tau = mean |f|`` of the last one (a host read)."""
+        if not self.isR3:
+            raise ValueError("resample_stats() needs compile(resample='r3')")
+        op = self._r3_ops.get("op")
+        if op is None:
+            return {"step": int(self._r3_state), "released": 0, "threshold": float("nan")}
+        return op.read_stats()
 
     def _ntk_op(self):
         """The trace evaluator of the full-batch program (``ops/ntk.py``), rebuilt with the program."""
@@ -612,8 +761,8 @@ class CollocationSolverND:
 
     @property
     def variables(self):
-        # (NTK and causal weights are not trained: no gradient is taken with respect to them)
-        return [self._flat()] + ([] if self.isNTK or self.isCausal else list(self.lambdas or []))
+        # (NTK and causal weights and the R3 mode's ones are not trained: no gradient is taken with respect to them)
+        return [self._flat()] + ([] if self.isNTK or self.isCausal or self.isR3 else list(self.lambdas or []))
 
     def _outside_sum_weights(self):
         """Per-point residual weights enter through MSE's outside sum (Adaptive_type 2 without
@@ -664,13 +813,14 @@ class CollocationSolverND:
         if eng is None:
             groups = [ParamGroup([self._flat()], lambda: self.tf_optimizer, 1.0)]
             bind = None
-            if self.isNTK or self.isCausal:   # the weights enter the loss but no optimizer owns them
+            if self.isNTK or self.isCausal or self.isR3:   # the weights enter the loss but no optimizer owns them
                 bind = lambda alias: {"params": alias[0], "lambdas": self.lambdas}  # noqa: E731
             else:
                 groups.append(ParamGroup(self.lambdas, lambda: self.tf_optimizer_weights, -1.0,
                                          self._lam_replicated()))
             eng = AdamEngine(self, prog, groups, n_steps_hint=n_hint, lambdas=self.lambdas, bind=bind,
-                             causal=self._causal_op(prog) if self.isCausal else None)
+                             causal=self._causal_op(prog) if self.isCausal else None,
+                             resample=self._r3_op(prog) if self.isR3 else None)
             self._programs[key] = eng
         return eng
 
@@ -703,6 +853,9 @@ class CollocationSolverND:
         ctx = self.dist_ctx
         if self.isCausal and batch_sz is not None:
             raise ValueError("causal training weights need full-batch steps (the bins' residual means cover every "
+                             "collocation point): batch_sz must be None")
+        if self.isR3 and batch_sz is not None:
+            raise ValueError("R3 resampling needs full-batch steps (the threshold is the mean of |f| over every "
                              "collocation point): batch_sz must be None")
         batches = self.minibatches(batch_sz)
         if self.verbose and ctx.rank == 0:
@@ -769,6 +922,8 @@ class CollocationSolverND:
                     if (ep + 1) % self.log_every == 0 or ep + 1 == tf_iter:
                         progress(ep + 1, float(loss))
             bar.close()
+            if self.isR3:   # the final population, into X_f_local and every other built program
+                self._r3_sync()
             st = self._state
             self.min_loss["adam"] = float(st["best_loss"])   # (device sync: the phase is done)
             self.fit_info["adam"] = {"steps": int(tf_iter), "wall_s": time.perf_counter() - t_adam}
@@ -776,6 +931,8 @@ class CollocationSolverND:
             self._best_flat["adam"] = st["best_flat"].clone()
             self.best_model["adam"] = _FlatModel(self.u_model, self._best_flat["adam"])
         if newton_iter > 0:
+            if self.isR3:   # L-BFGS runs on the frozen population (a program built since then takes it here)
+                self._r3_sync()
             self._fit_lbfgs(newton_iter, newton_eager)
         self._select_overall(start_epoch, tf_iter)
 

@@ -134,6 +134,30 @@ class LossProgram:
         self.X_all = cat(order)
         self.X_hi = cat(hi) if hi else None
 
+    def segment_rows(self, si):
+        """The rows of segment ``si`` in ``X_all`` (a view)."""
+        s = self.segments[si]
+        return self.X_all[s.offset:s.offset + s.n]
+
+    def refresh_points(self, si, X=None):
+        """Points of segment ``si`` that moved (resampling, ops/r3.py): every copy this program keeps is
+        brought up to date in place - ``X`` (default: the rows as they are) goes into the segment's rows
+        of ``X_all``, the segment's own ``X`` becomes a view of those rows (the jet path hands it to the
+        user's callables) and a one-launch step that was built re-gathers its point set.  Buffers keep
+        their addresses, so captured graphs stay valid.  High-order segments also live in ``X_hi`` and in
+        the high-order kernels' scratch layout and are refused."""
+        s = self.segments[si]
+        if s.hi:
+            raise ValueError(f"segment {s.name!r} runs on the high-order plan; its points cannot be refreshed")
+        rows = self.segment_rows(si)
+        if X is not None:
+            with torch.no_grad():
+                rows.copy_(torch.as_tensor(X, dtype=self.dtype).reshape(-1, self.d_in))
+        s.X = rows
+        fs = getattr(self, "_fused_step", None)
+        if fs is not None:
+            fs.refresh_points()
+
     @property
     def mixed(self):
         return self.plan_hi is not None

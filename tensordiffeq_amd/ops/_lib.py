@@ -19,7 +19,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TDQ_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "csrc", "libtdq_hip.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 _lock = threading.Lock()
 _lib = None
@@ -94,6 +94,10 @@ def _declare(lib):
         # causal training weights (csrc/causal.hip, ops/causal.py)
         "tdq_causal_work_doubles": (I, [I]),
         "tdq_causal_update": (I, [P, D, P, P, P, I, I, P, P, P, P, P, P]),
+        # R3 resampling of the collocation points (csrc/r3.hip, ops/r3.py)
+        "tdq_r3_work_doubles": (I, [I]),
+        "tdq_r3_count_ints": (I, [I]),
+        "tdq_r3_resample": (I, [P, D, P, P, c.c_uint64, P, I, P, I, L, I, I, P, P, P, P]),
         "tdq_lbfgs_nst": (I, []),
         "tdq_lbfgs_ticket_ints": (I, []),
         "tdq_lbfgs_update": (I, [P] * 14 + [I] * 6 + [D] * 4 + [I, P]),

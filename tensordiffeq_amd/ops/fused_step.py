@@ -526,6 +526,7 @@ class FusedStepOp:
         dev = prog.device
         self.mixed = _mixed(prog)
         self.layout = "split" if self.mixed else "plain"
+        self.idx = idx   # (kept on the host: refresh_points / segment_start are rare)
         ix = torch.tensor(idx, dtype=torch.long, device=dev)
         X_f = prog.X_all[ix.clamp_min(0)].clone()
         X_f[ix < 0] = 0.0
@@ -574,6 +575,27 @@ class FusedStepOp:
         if self.fop2 is not None:   # the side chain's loss blocks write rows [0, prow) of the same buffer
             self.fop2.partials = self.lpart[:self.prow * self.nacc]
             self._side = torch.cuda.Stream(device=dev)
+
+    def refresh_points(self):
+        """Re-gather the fused point set from ``prog.X_all`` in place (points that moved: resampling)."""
+        with torch.no_grad():
+            ix = torch.tensor(self.idx, dtype=torch.long, device=self.X.device)
+            X_f = self.prog.X_all[ix.clamp_min(0)]
+            X_f[ix < 0] = 0.0
+            self.X.copy_(X_f)
+
+    def segment_start(self, si):
+        """The first row of segment ``si`` in the fused point set when its points are the consecutive
+        rows ``start + i`` there (a group of one segment), else None."""
+        s = self.prog.segments[si]
+        ix = torch.tensor(self.idx, dtype=torch.long)
+        pos = torch.nonzero(ix == s.offset).reshape(-1)
+        if s.n < 1 or pos.numel() != 1:
+            return None
+        start = int(pos[0])
+        if start + s.n > ix.numel() or not torch.equal(ix[start:start + s.n], torch.arange(s.offset, s.offset + s.n)):
+            return None
+        return start
 
     def run(self, saved, J, work, flat, pack=True, prebook=None):
         """The step's gradient slabs and loss partials (the fused launch; mixed programs: plus the

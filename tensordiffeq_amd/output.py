@@ -36,3 +36,6 @@ def print_screen(model, discovery_model=False):
     if getattr(model, "isCausal", False):
         print(f"adaptive weights: causal ({model.causal_bins} time bins, eps schedule {model.causal_eps}, "
               f"checked every {model.causal_every} Adam steps)")
+    if getattr(model, "isR3", False):
+        print(f"collocation points: R3 resampling after every Adam step (retain |f| > mean |f|, release the rest "
+              f"into the domain box; seed {model.resample_seed}), frozen during L-BFGS")
